@@ -21,6 +21,12 @@ own job ("replicas", weak scaling, no data-path collective); value = jobs/s over
 `--gpus N` alone starts N ranks (bench_launch.py: a GPU-free parent forks N fresh processes
 with RANK / LOCAL_RANK / WORLD_SIZE set); under torch.distributed.run WORLD_SIZE must equal
 --gpus or the run exits 2.
+
+A plain run (`--gpus G --steps N --warmup W`) sets up, warms up, times the N steps and prints
+the headline line (value, ms_per_step, the workload); `--dump-outputs DIR` also writes what
+the last timed step returned (mu, var, alpha and a seeded sample of the factor U) as
+DIR/<name>.npy.  Everything below runs only with `--full`, after the headline is measured.
+
 Beside it, key `split_predict`: BASELINE config 5 (split-kernel block prediction, 1M test points)
 SHARDED over all ranks with the RCCL broadcast of U / wt and an all_gather of the shards
 (strong scaling; `--no-split` skips it).
@@ -35,7 +41,8 @@ events on the stream it runs on over one instrumented step; `cpu_baseline` = the
 median of 3 after a warm-up; --cpu-n / --cpu-np shrink it, and the stages are then scaled by
 their complexity to the job).
 
-Output: rank 0 prints the ONE JSON line on stdout as soon as the headline, its instrumented
+Output: rank 0 prints the ONE JSON line on stdout -- in a plain run right after the timed
+steps; with `--full` as soon as the headline, its instrumented
 step and the CPU baseline are measured -- BEFORE the C5 leg, so a failure or hang inside the
 leg (RCCL across ranks) cannot cost the headline.  The C5 leg's own JSON object follows on
 stderr (key `split_predict`), and a watchdog ends the process if the leg outlives
@@ -153,7 +160,16 @@ def parse():
     # LOCAL_RANK modulo the device count): gloo carries the collectives (RCCL refuses two
     # ranks on one device); the driver's runs use the default nccl (= RCCL), one rank per GPU
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the instrumented steps (stage breakdown, "
+                         "K-build rates, store ceilings, roofline), the CPU baseline and the C5 "
+                         "split-predict leg; the --no-* / --cpu-* / --split-* options shape these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (mu, var, "
+                         "alpha, a seeded sample of the factor U) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.cpu_n = a.cpu_n or a.n
     a.cpu_np = a.cpu_np or a.npred
     return a
@@ -401,6 +417,38 @@ def split_leg(a, world, rank, local):
     return out
 
 
+U_SAMPLE = 1 << 20  # entries of the factor written by --dump-outputs (8 MB)
+
+
+def u_sample_index(n):
+    """The (i, j), i <= j, 0-based positions of `U_sample` for an N = n factor."""
+    return np.sort(np.random.default_rng(20240607).integers(0, n, size=(U_SAMPLE, 2)), axis=1)
+
+
+def dump_outputs(path, ctx, K, alpha, mu, var, n):
+    """--dump-outputs: what the last timed gpr_fit_predict returned, as float64 .npy files --
+    mu and var (np), alpha (N) in full, and `U_sample`: U_SAMPLE entries (i <= j) of the upper
+    Cholesky factor left in K (N x N column-major, 8 N^2 bytes: too large to write whole), at
+    positions drawn once from a fixed seed, so two builds run with the same arguments write
+    the same entries in the same order."""
+    os.makedirs(path, exist_ok=True)
+    ij = u_sample_index(n)
+    ctx.sync()
+    with torch.cuda.stream(ctx.stream):
+        at = torch.from_numpy(ij[:, 0] + ij[:, 1] * n).to(K.device)  # (i, j) at i + j N
+        u = K.view(-1)[at]
+    ctx.sync()
+    for name, t in (("mu", mu), ("var", var), ("alpha", alpha), ("U_sample", u)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
+
+
+def _close_group():
+    if dist.is_initialized():
+        with _StdoutToStderr():
+            dist.barrier()
+            dist.destroy_process_group()
+
+
 def main():
     a = parse()
     # --gpus N without a launcher: this process only forks N ranks and never touches the GPU;
@@ -485,6 +533,35 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ok = bool(torch.isfinite(mu).all().item() and torch.isfinite(var).all().item())
+    if a.dump_outputs and rank == 0:  # (before anything below reuses the buffers)
+        dump_outputs(a.dump_outputs, ctx, K, alpha, mu, var, N)
+
+    headline = {
+        "metric": "GP-fit+predict wall-time and K-build GB/s + POTRF TFLOP/s at N=32768",
+        "value": world / dt,
+        "unit": "GP jobs/s (fit N=%d + posterior mean/var np=%d, per GPU)" % (N, NP),
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": dt * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (x~U[0,1)^(d x N) seeded, y=sin(sum x)^2)",
+        "config": {"workload": f"{config_label(a)} fit+posterior: {a.kernel}, N={N}, d={d}, "
+                               f"np={NP}",
+                   "N": N, "d": d, "np": NP, "kernel": a.kernel, "nb": a.nb,
+                   "parallelism": f"replicas x{world}"},
+        "results_finite": ok,
+        "dist_backend": a.dist_backend if world > 1 else None,
+        "physical_gpus": ndev,
+    }
+    if not a.full:  # the plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        _close_group()
+        return
 
     # ---- instrumented steps (HIP events on the context stream) --------------------------
     # (a) the unfused reference order (gpr_kernel, gpr_potrf_upper, gpr_potrs_upper,
@@ -567,22 +644,7 @@ def main():
     out = None
     if rank == 0:
         out = {
-            "metric": "GP-fit+predict wall-time and K-build GB/s + POTRF TFLOP/s at N=32768",
-            "value": world / dt,
-            "unit": "GP jobs/s (fit N=%d + posterior mean/var np=%d, per GPU)" % (N, NP),
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": dt * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (x~U[0,1)^(d x N) seeded, y=sin(sum x)^2)",
-            "config": {"workload": f"{config_label(a)} fit+posterior: {a.kernel}, N={N}, d={d}, "
-                                   f"np={NP}",
-                       "N": N, "d": d, "np": NP, "kernel": a.kernel, "nb": a.nb,
-                       "parallelism": f"replicas x{world}"},
+            **headline,
             "kbuild_GBps": kbuild_gbs,
             "kbuild_hbm_frac": kbuild_gbs / HBM_PEAK_GBS,
             "kbuild_ms": kb_ms,
@@ -630,9 +692,6 @@ def main():
                 # rocprof MFMA counters of the same kernel (committed profile of this command)
                 "pmc_mfma": pmc_mfma(dominant[0], N, NP),
             },
-            "results_finite": ok,
-            "dist_backend": a.dist_backend if world > 1 else None,
-            "physical_gpus": ndev,
         }
         if world > 1 and a.dist_backend == "gloo":
             out["rehearsal"] = (f"{world} ranks sharing {ndev} device(s) over gloo: plumbing "
@@ -676,10 +735,7 @@ def main():
         wd.cancel()
         if rank == 0:
             print(json.dumps({"split_predict": split}), file=sys.stderr, flush=True)
-    if dist.is_initialized():
-        with _StdoutToStderr():
-            dist.barrier()
-            dist.destroy_process_group()
+    _close_group()
 
 
 if __name__ == "__main__":

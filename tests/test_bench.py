@@ -87,7 +87,7 @@ def test_bench_gpus2_spawns_two_ranks():
     (sharing cuda:0 over gloo), and stdout is ONE JSON line with n_gpus = 2 and the world's
     value (2 replicas' jobs/s)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
                         "--dist-backend", "gloo", "--n", "4096", "--np", "1024", "--steps", "1",
                         "--warmup", "0", "--no-cpu-baseline", "--no-split-full", "--no-se-ard"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -100,6 +100,60 @@ def test_bench_gpus2_spawns_two_ranks():
     assert '"split_predict"' in r.stderr
     split = [json.loads(x) for x in r.stderr.splitlines() if x.startswith('{"split_predict"')]
     assert split and split[-1]["split_predict"]["n_gpus"] == 2, split
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain run prints the headline line only (nothing of the `--full` legs) and
+    `--dump-outputs` writes what the last timed gpr_fit_predict returned: mu, var, alpha and
+    the seeded sample of the factor, checked against the oracle on the bench's own seeded data.
+    Size and tolerances for mu / var are smoke()'s (d = 3, N = 300: three 128-tiles, ragged);
+    alpha and U are held to test_gpu_parity's fit_predict bounds (rtol 1e-8, atol 1e-10 of the
+    largest entry: cond(K) <= (N sigma^2 + sigma_n^2) / sigma_n^2 = 3e4, so the factorisation's
+    error N eps cond(K) stays under 1e-9 relative)."""
+    import importlib.util
+
+    import numpy as np
+
+    from oracle import gpr_oracle as O
+
+    d, n, m = 3, 300, 77
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
+                        "2", "--warmup", "1", "--n", str(n), "--d", str(d), "--np", str(m),
+                        "--kernel", "SE+WN", "--dump-outputs", str(tmp_path / "dump")],
+                       env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["results_finite"]
+    assert out["value"] == pytest.approx(1e3 / out["ms_per_step"])
+    assert out["dtype"] == "f64" and out["higher_is_better"] is True
+    for key in ("cpu_baseline", "split_predict", "roofline", "stage_ms_unfused",
+                "kbuild_store_ceiling"):
+        assert key not in out
+    assert "split_predict" not in r.stderr
+
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(got) == ["U_sample", "alpha", "mu", "var"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    x, y, xp = O.synthetic(d, n, m)
+    kinds = [O.SE, O.WN]
+    hp = O.default_hp(kinds, d)
+    mu, var = O.predict(kinds, hp, x, y, xp, diagonal_var=True)
+    np.testing.assert_allclose(got["mu"], mu, rtol=1e-8, atol=1e-12)
+    np.testing.assert_allclose(got["var"], var, rtol=1e-8, atol=1e-12)
+    U = O.chol_upper(O.kernel(kinds, hp, x))
+    a_o = O.cho_solve_upper(U, y)
+    np.testing.assert_allclose(got["alpha"], a_o, rtol=1e-8, atol=1e-10 * np.abs(a_o).max())
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ij = bench.u_sample_index(n)
+    assert got["U_sample"].shape == (bench.U_SAMPLE,)
+    np.testing.assert_allclose(got["U_sample"], U[ij[:, 0], ij[:, 1]], rtol=1e-8,
+                               atol=1e-10 * np.abs(U).max())
 
 
 def test_workload_label_names_the_config():

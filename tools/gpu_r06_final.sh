@@ -7,6 +7,6 @@ if [ "${1:-tests}" = tests ]; then
   timeout -k 10 1080 python -u -m pytest tests -x -q -m gpu --timeout 400 --timeout-method thread -p no:cacheprovider > $O/tests.log 2>&1 || exit 1
 else
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 2
-  timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || exit 3
+  timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit 3
 fi
 echo done

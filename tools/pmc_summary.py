@@ -104,7 +104,7 @@ def main():
             kernels.setdefault(k, {})["mfma_largest_launch"] = m
     out = {"config": {"N": n, "np": npred},
            "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs of "
-                     "`bench.py --steps 1 --warmup 0 --no-cpu-baseline`; FETCH_SIZE x2 (gfx950 "
+                     "`bench.py --full --steps 1 --warmup 0 --no-cpu-baseline`; FETCH_SIZE x2 (gfx950 "
                      "16-B/lane correction), KiB -> bytes; WRITE_SIZE of 8-B/lane stores is "
                      "uncalibrated (MI355X_MICROARCH.md, HBM section)",
            "kernels": kernels}
