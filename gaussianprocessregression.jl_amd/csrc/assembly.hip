@@ -43,7 +43,7 @@ __global__ void scale_inputs_kernel(KParams kp, const double* __restrict__ X, in
     const int p = (int)(t / total);
     const size_t r = t - p * total;
     const int k = (int)(r % d);
-    xs[t] = X[r] * kp.l[p][k];
+    xs[t] = X[r] * kp.l[(size_t)p * d + k];
   }
 }
 
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
 #pragma unroll
       for (int k = 0; k < D; ++k) xr[k] = xrow[k];
     }
-    const double s2 = kp.sigma[p] * kp.sigma[p];
+    const double s2 = kp.sig[p] * kp.sig[p];  // (any number of parts: the device table)
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int j = j0 + wv + 4 * c;  // wave-uniform column
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const doubl
 #pragma unroll
       for (int k = 0; k < D; ++k) xr[k] = xrow[k];
     }
-    const double s2 = kp.sigma[p] * kp.sigma[p];
+    const double s2 = kp.sig[p] * kp.sig[p];  // (any number of parts: the device table)
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int j = j0 + wv + 4 * c;
@@ -228,15 +228,15 @@ __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
       const double q = xa[k] - xb[k];
       s = fma(q, q, s);
     }
-    double Kp = kp.sigma[p] * kp.sigma[p] * exp(-1.0 * s);
+    double Kp = kp.sig[p] * kp.sig[p] * exp(-1.0 * s);
     if (a == b) Kp += kp.eps;
     double v;
     if (which == 0) {
-      v = (2.0 / fabs(kp.sigma[p])) * Kp;
+      v = (2.0 / fabs(kp.sig[p])) * Kp;
     } else {
       const int k = which - 1;
       const double dx = X[(size_t)a * d + k] - X[(size_t)b * d + k];
-      v = -2.0 * kp.l[p][k] * Kp * (dx * dx);
+      v = -2.0 * kp.l[(size_t)p * d + k] * Kp * (dx * dx);
     }
     DK[(size_t)a + (size_t)b * ld] = v;
   }
@@ -486,7 +486,7 @@ void launch_sym(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, double
   const int nt = (n + KT - 1) / KT;
   const long long nblk = (long long)nt * (nt + 1) / 2;
   if constexpr (D > 0) {
-    if (vec_store_ok(K, ldk)) {
+    if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {  // (their LDS tables hold KMAXP parts)
       const int grid = (int)std::min<long long>(nblk, kbuild_grid());
       const size_t lds_bytes = sizeof(double) * (KT_LDS + 256 * kp.nse);
       kmat_sym2_kernel<D><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
@@ -502,7 +502,7 @@ void launch_cross(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, cons
   const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
   const unsigned nblk = (unsigned)((long long)nti * ntj);
   if constexpr (D > 0) {
-    if (vec_store_ok(K, ldk)) {
+    if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {  // (their LDS tables hold KMAXP parts)
       const int grid = (int)std::min<long long>(nblk, kbuild_grid());
       const size_t lds_bytes = sizeof(double) * (KT * D + 256 * kp.nse);
       kmat_cross2_kernel<D><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk,
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(256) void gram_center_kernel(const double* __restri
     if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
     __syncthreads();
   }
-  if (threadIdx.x == 0) c[p * KMAXD + k] = red[0] / (double)cnt;
+  if (threadIdx.x == 0) c[p * d + k] = red[0] / (double)cnt;
 }
 
 // out[p][blk][s][lane] = scale * y[16 blk + (lane & 15)][4 s + (lane >> 4)] (0 past d or n);
@@ -568,7 +568,7 @@ __global__ void gram_prep_kernel(const double* __restrict__ xs, int n, int d, in
     const int blk = (int)(r2 % nblk), p = (int)(r2 / nblk);
     const int a = blk * 16 + (lane & 15), k = 4 * s + (lane >> 4);
     const double* xa = xs + ((size_t)p * n + a) * d;
-    const double* cp = c + p * KMAXD;
+    const double* cp = c + (size_t)p * d;
     out[t] = (a < n && k < d) ? scale * (xa[k] - cp[k]) : 0.0;
     if (nrm && s == 0 && lane < 16) {
       double q = 0.0;
@@ -751,6 +751,245 @@ __global__ __launch_bounds__(256, 4) void kmat_crossg_kernel(KParams kp, const d
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
     gram_tile<S, false>(kp, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
+    __syncthreads();
+    gram_to_lds(v, T);
+    __syncthreads();
+    const int i = i0 + 2 * l32;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int jl = cg + 8 * c, j = j0 + jl;
+      if (j < m)
+        store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, T[jl * (KT + 1) + 2 * l32],
+                   T[jl * (KT + 1) + 2 * l32 + 1]);
+    }
+  }
+}
+
+// ---- the Gram form for any d: run-time S = ceil(d/4) -------------------------------------
+// gram_tile<S> holds all 2 x 2 x S operand registers of a wave's quadrant, so S is compiled in
+// (d <= 20).  Here the k-steps are walked in chunks of GR_CH = 4 (16 dimensions): a chunk's
+// 2 x 4 row and 2 x 4 column operands are 16 coalesced 512-B wave loads, the next chunk's are
+// issued before the current chunk's MFMA chain (four independent 16 x 16 accumulators, started
+// from -|y_a|^2 - |y_b|^2 as in gram_tile), and the last chunk is ragged by whole k-steps:
+// steps past S enter as zero operands, which leave every accumulator bit for bit as it was
+// (padding inside a step is already zero in the prepared operands).  The exponential, the
+// diagonal rule (D = 0 exactly, eps per part), the part sum and the tile stores are those of
+// kmat_symg_kernel / kmat_crossg_kernel.  96 operand/accumulator registers whatever d is.
+// ACC: the launch ADDS its parts to the K already stored (part groups beyond the first KMAXP,
+// launch_gram_groups): the tile's current values are read through LDS (coalesced 16-B loads,
+// the store pattern backwards) into the MFMA layout, then each part's term is added in part
+// order, so the element sum stays ((p1 + p2) + p3) + ... across launches.
+constexpr int GR_CH = 4;  // k-steps per chunk
+
+template <bool DIAG>
+__device__ __forceinline__ void gram_tile_rt(const KParams& kp, int S, const double* __restrict__ gA,
+                                             const double* __restrict__ gB,
+                                             const double* __restrict__ nA,
+                                             const double* __restrict__ nB, int nblkA, int nblkB,
+                                             int i0, int j0, const double* tabs, gd4 (&v)[2][2]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wr = w & 1, wc = w >> 1;
+  const int ba = (i0 >> 4) + 2 * wr, bb = (j0 >> 4) + 2 * wc;  // first 16-blocks
+  const int nch = (S + GR_CH - 1) / GR_CH;
+  for (int p = 0; p < kp.nse; ++p) {
+    const double* Ap = gA + ((size_t)p * nblkA + ba) * S * 64 + lane;
+    const double* Bp = gB + ((size_t)p * nblkB + bb) * S * 64 + lane;
+    const double* nAp = nA + (size_t)p * nblkA * 16 + ba * 16 + (lane >> 4);
+    const double* nBp = nB + (size_t)p * nblkB * 16 + bb * 16 + (lane & 15);
+    // operand of 16-block h, k-step s (wave-uniform bound: zero past S)
+    auto load_chunk = [&](int ch, double (&a)[2][GR_CH], double (&b)[2][GR_CH]) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < GR_CH; ++s) {
+          const int st = GR_CH * ch + s;
+          const bool in = st < S;
+          a[h][s] = in ? Ap[((size_t)h * S + st) * 64] : 0.0;
+          b[h][s] = in ? Bp[((size_t)h * S + st) * 64] : 0.0;
+        }
+    };
+    double a[2][GR_CH], b[2][GR_CH];
+    load_chunk(0, a, b);
+    double nr[2][4], nc[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) nr[h][q] = nAp[16 * h + 4 * q];
+      nc[h] = nBp[16 * h];
+    }
+    gd4 acc[2][2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[rb][cb][q] = nr[rb][q] + nc[cb];
+    for (int ch = 0; ch < nch; ++ch) {
+      double an[2][GR_CH], bn[2][GR_CH];
+      if (ch + 1 < nch) load_chunk(ch + 1, an, bn);  // in flight behind this chunk's MFMAs
+#pragma unroll
+      for (int s = 0; s < GR_CH; ++s)
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb)
+            acc[rb][cb] =
+                __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][s], b[cb][s], acc[rb][cb], 0, 0, 0);
+      if (ch + 1 < nch) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int s = 0; s < GR_CH; ++s) {
+            a[h][s] = an[h][s];
+            b[h][s] = bn[h][s];
+          }
+      }
+    }
+    const double* ts = tabs + 256 * p;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          double x = acc[rb][cb][q];  // -D
+          bool on_diag = false;
+          if (DIAG) {
+            on_diag = wr == wc && rb == cb && (lane >> 4) + 4 * q == (lane & 15);
+            if (on_diag) x = 0.0;
+          }
+          double t = kexp_s2(-x, ts);
+          if (DIAG && on_diag) t += kp.eps;
+          v[rb][cb][q] += t;
+          if ((q + 1) % GRAM_EXPG == 0) __builtin_amdgcn_sched_barrier(0);
+        }
+  }
+  if (DIAG && kp.has_noise && wr == wc) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if ((lane >> 4) + 4 * q == (lane & 15)) v[rb][rb][q] += kp.noise2;
+  }
+}
+
+// v <- 0, or (ACC) the tile of K at (i0, j0) (rows < nr, columns < nc; 0 outside) through T
+template <bool ACC>
+__device__ __forceinline__ void gram_tile_init(const double* __restrict__ K, size_t ldk, int i0,
+                                               int j0, int nr, int nc, double* T,
+                                               gd4 (&v)[2][2]) {
+  if (!ACC) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) v[rb][cb] = gd4{0.0, 0.0, 0.0, 0.0};
+    return;
+  }
+  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
+  const int lane = t & 63, w = t >> 6;
+  __syncthreads();  // previous tile's LDS reads are done
+  const int i = i0 + 2 * l32;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int jl = cg + 8 * c, j = j0 + jl;
+    double e0 = 0.0, e1 = 0.0;
+    if (j < nc) {
+      const double* src = K + (size_t)i + (size_t)j * ldk;
+      if (i + 1 < nr) {
+        const kd2 pr = *reinterpret_cast<const kd2*>(src);
+        e0 = pr[0];
+        e1 = pr[1];
+      } else if (i < nr) {
+        e0 = src[0];
+      }
+    }
+    T[jl * (KT + 1) + 2 * l32] = e0;
+    T[jl * (KT + 1) + 2 * l32 + 1] = e1;
+  }
+  __syncthreads();
+  const int r0 = 32 * (w & 1) + (lane >> 4), c0 = 32 * (w >> 1) + (lane & 15);
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[rb][cb][q] = T[(c0 + 16 * cb) * (KT + 1) + r0 + 16 * rb + 4 * q];
+}
+
+template <bool ACC>
+__global__ __launch_bounds__(256, 2) void kmat_symgr_kernel(KParams kp, int S,
+                                                            const double* __restrict__ gA,
+                                                            const double* __restrict__ gB,
+                                                            const double* __restrict__ nrm,
+                                                            int nblk, int n, double* __restrict__ K,
+                                                            size_t ldk, int ntiles) {
+  extern __shared__ double dyn_lds[];  // KT_LDS doubles (tile), then nse exp tables
+  double* T = dyn_lds;
+  double* tabs = dyn_lds + KT_LDS;
+  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
+  load_part_tables(kp, tabs);
+  __syncthreads();
+  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+    int bi, bj;
+    tri_tile(bid, &bi, &bj);
+    const int i0 = bi * KT, j0 = bj * KT;
+    gd4 v[2][2];
+    gram_tile_init<ACC>(K, ldk, i0, j0, n, n, T, v);
+    if (bi == bj)
+      gram_tile_rt<true>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+    else
+      gram_tile_rt<false>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+    __syncthreads();  // previous tile's LDS reads are done
+    gram_to_lds(v, T);
+    __syncthreads();
+    const int i = i0 + 2 * l32;
+    if (bi == bj) {
+      // diagonal tile: the strictly-lower half mirrors the upper, so K == K^T bitwise
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int jl = cg + 8 * c, j = j0 + jl, r0 = 2 * l32, r1 = 2 * l32 + 1;
+        const double e0 = r0 <= jl ? T[jl * (KT + 1) + r0] : T[r0 * (KT + 1) + jl];
+        const double e1 = r1 <= jl ? T[jl * (KT + 1) + r1] : T[r1 * (KT + 1) + jl];
+        if (j < n) store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, e0, e1);
+      }
+      continue;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int jl = cg + 8 * c, j = j0 + jl;
+      if (j < n)
+        store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, T[jl * (KT + 1) + 2 * l32],
+                   T[jl * (KT + 1) + 2 * l32 + 1]);
+    }
+    const int jj = j0 + 2 * l32;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int il = cg + 8 * c;
+      if (i0 + il < n)
+        store_pair(K, (size_t)jj + (size_t)(i0 + il) * ldk, jj < n, jj + 1 < n,
+                   T[(2 * l32) * (KT + 1) + il], T[(2 * l32 + 1) * (KT + 1) + il]);
+    }
+  }
+}
+
+template <bool ACC>
+__global__ __launch_bounds__(256, 2) void kmat_crossgr_kernel(
+    KParams kp, int S, const double* __restrict__ gA, const double* __restrict__ gB,
+    const double* __restrict__ nrmA, const double* __restrict__ nrmB, int nblkA, int nblkB, int n,
+    int m, double* __restrict__ K, size_t ldk, int ntile_i, int ntiles) {
+  extern __shared__ double dyn_lds[];
+  double* T = dyn_lds;
+  double* tabs = dyn_lds + KT_LDS;
+  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
+  load_part_tables(kp, tabs);
+  __syncthreads();
+  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+    const int bi = __builtin_amdgcn_readfirstlane(bid % ntile_i);
+    const int bj = __builtin_amdgcn_readfirstlane(bid / ntile_i);
+    const int i0 = bi * KT, j0 = bj * KT;
+    gd4 v[2][2];
+    gram_tile_init<ACC>(K, ldk, i0, j0, n, m, T, v);
+    gram_tile_rt<false>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
     __syncthreads();
     gram_to_lds(v, T);
     __syncthreads();
@@ -1033,20 +1272,34 @@ __global__ __launch_bounds__(256, KU_MINB) void kmat_symu_kernel(KParams kp, con
   }
 }
 
-// the Gram form (MFMA distance) for d <= 20 unless the context asks for the reference's
-// difference form (GPR_KBUILD_EXACT knob)
-inline bool gram_enabled(const gpr_ctx* ctx, int d) { return !ctx->kbuild_exact && d <= 4 * 5; }
+// the Gram form (MFMA distance) up to d = GPR_KBUILD_GRAM_MAXD unless the context asks for the
+// reference's difference form (GPR_KBUILD_EXACT knob); GRAM_CT_MAXD: the largest d of the
+// kernels compiled per S = ceil(d/4) (gram_tile<S>, the upper-only build) -- above it the
+// run-time-S tile (gram_tile_rt)
+constexpr int GRAM_CT_MAXD = 4 * 5;
+inline bool gram_enabled(const gpr_ctx* ctx, int d) {
+  return !ctx->kbuild_exact && d <= ctx->kbuild_gram_maxd;
+}
 
-template <int S>
+// doubles of the centres' buffer: nse x d, and never below the old fixed 4 x 64 so that no
+// call inside that envelope re-allocates it
+inline size_t gram_centres_cap(const KParams& kp) {
+  return std::max((size_t)kp.nse * kp.d, (size_t)256);
+}
+
+// S > 0: the kernels compiled for S k-steps; S = 0: the run-time-S kernels (any d), which with
+// acc add their parts to the K already stored (launch_gram_groups)
+template <int SC>
 int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
-                int m, int same, double* K, int ldk) {
+                int m, int same, double* K, int ldk, int acc = 0) {
   const int d = kp.d;
+  const int S = SC > 0 ? SC : (d + 3) / 4;
   const int nbA = ((n + KT - 1) / KT) * (KT / 16);
   const int nbB = same ? nbA : ((m + KT - 1) / KT) * (KT / 16);
   const size_t opA = (size_t)kp.nse * nbA * S * 64, opB = same ? 0 : (size_t)kp.nse * nbB * S * 64;
   const size_t nA = (size_t)kp.nse * nbA * 16, nB = same ? 0 : (size_t)kp.nse * nbB * 16;
   // dgA: row operands + row norms; dgB: column operands + column norms (cross only)
-  GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, (size_t)KMAXP * KMAXD));
+  GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, gram_centres_cap(kp)));
   GPR_TRY(ensure_buf(ctx, &ctx->dgA, &ctx->gA_cap, opA + nA + (same ? opA : 0)));
   if (!same) GPR_TRY(ensure_buf(ctx, &ctx->dgB, &ctx->gB_cap, opB + nB));
   double* A = ctx->dgA;
@@ -1068,15 +1321,28 @@ int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const 
     const int nt = (n + KT - 1) / KT;
     const long long nblk = (long long)nt * (nt + 1) / 2;
     const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-    kmat_symg_kernel<S><<<grid, 256, lds_bytes, ctx->stream>>>(kp, A, B, nrmA, nbA, n, K,
-                                                               (size_t)ldk, (int)nblk);
+    if constexpr (SC > 0)
+      kmat_symg_kernel<SC><<<grid, 256, lds_bytes, ctx->stream>>>(kp, A, B, nrmA, nbA, n, K,
+                                                                  (size_t)ldk, (int)nblk);
+    else if (acc)
+      kmat_symgr_kernel<true><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
+                                                                     (size_t)ldk, (int)nblk);
+    else
+      kmat_symgr_kernel<false><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
+                                                                      (size_t)ldk, (int)nblk);
   } else {
     const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
     const long long nblk = (long long)nti * ntj;
     const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-    kmat_crossg_kernel<S><<<grid, 256, lds_bytes, ctx->stream>>>(kp, A, B, nrmA, nrmB, nbA, nbB,
-                                                                 n, m, K, (size_t)ldk, nti,
-                                                                 (int)nblk);
+    if constexpr (SC > 0)
+      kmat_crossg_kernel<SC><<<grid, 256, lds_bytes, ctx->stream>>>(
+          kp, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
+    else if (acc)
+      kmat_crossgr_kernel<true><<<grid, 256, lds_bytes, ctx->stream>>>(
+          kp, S, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
+    else
+      kmat_crossgr_kernel<false><<<grid, 256, lds_bytes, ctx->stream>>>(
+          kp, S, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
   }
   LAUNCH_CHECK(ctx);
   return 0;
@@ -1089,7 +1355,7 @@ int launch_gram_upper(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, 
   const int d = kp.d;
   const int nbA = ((n + KT - 1) / KT) * (KT / 16);
   const size_t opA = (size_t)NSE * nbA * S * 64, nA = (size_t)NSE * nbA * 16;
-  GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, (size_t)KMAXP * KMAXD));
+  GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, gram_centres_cap(kp)));
   GPR_TRY(ensure_buf(ctx, &ctx->dgA, &ctx->gA_cap, 2 * opA + nA));
   double* A = ctx->dgA;
   double* nrmA = A + opA;
@@ -1184,6 +1450,7 @@ int launch_gram_upper_s(gpr_ctx* ctx, const KParams& kp, const double* xs, int n
 
 int launch_gram_any(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
                     int m, int same, double* K, int ldk) {
+  if (kp.d > GRAM_CT_MAXD) return launch_gram<0>(ctx, kp, xs, n, xps, m, same, K, ldk);
   switch ((kp.d + 3) / 4) {
     case 1: return launch_gram<1>(ctx, kp, xs, n, xps, m, same, K, ldk);
     case 2: return launch_gram<2>(ctx, kp, xs, n, xps, m, same, K, ldk);
@@ -1191,6 +1458,24 @@ int launch_gram_any(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, co
     case 4: return launch_gram<4>(ctx, kp, xs, n, xps, m, same, K, ldk);
     default: return launch_gram<5>(ctx, kp, xs, n, xps, m, same, K, ldk);
   }
+}
+
+// More than KMAXP SE parts (the fused kernels' LDS tables hold KMAXP): the first KMAXP parts by
+// the kernels any description of <= KMAXP parts takes, without the noise; then one accumulate
+// launch per further group of up to KMAXP parts, the last of which adds sigma_n^2 (add_noise!
+// comes after the part sum, src/compose_covar.jl:52-71).  xs / xps: all parts' scaled points.
+int launch_gram_groups(gpr_ctx* ctx, const KParams& kp, const double* xs, int n,
+                       const double* xps, int m, int same, double* K, int ldk) {
+  for (int p0 = 0; p0 < kp.nse; p0 += KMAXP) {
+    const int cnt = std::min(KMAXP, kp.nse - p0);
+    const bool last = p0 + cnt >= kp.nse;
+    const KParams g = kparams_group(kp, p0, cnt, last ? kp.has_noise : 0);
+    const double* gx = xs + (size_t)p0 * n * kp.d;
+    const double* gxp = same ? nullptr : xps + (size_t)p0 * m * kp.d;
+    if (p0 == 0) GPR_TRY(launch_gram_any(ctx, g, gx, n, gxp, m, same, K, ldk));
+    else GPR_TRY(launch_gram<0>(ctx, g, gx, n, gxp, m, same, K, ldk, 1));
+  }
+  return 0;
 }
 
 #define DISPATCH_D(FN, ...)                 \
@@ -1258,18 +1543,20 @@ int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kp, const double* dX, int 
     // one SE part: both halves computed by the column build (store-bound: one exponential per
     // element is cheaper than the mirrored tiles' store pattern); more parts: upper tiles
     // computed once and mirrored through LDS (the exponentials dominate)
-    if (gram_enabled(ctx, kp.d) && kp.nse <= 1)
+    if (gram_enabled(ctx, kp.d) && kp.d <= GRAM_CT_MAXD && kp.nse <= 1)
       return kp.nse == 1 ? launch_gram_upper_s<1>(ctx, kp, ctx->dxs, n, dK, ldk, 1)
                          : launch_gram_upper_s<2>(ctx, kp, ctx->dxs, n, dK, ldk, 1);
     if (gram_enabled(ctx, kp.d) && vec_store_ok(dK, ldk))
-      return launch_gram_any(ctx, kp, ctx->dxs, n, nullptr, n, 1, dK, ldk);
+      return kp.nse > KMAXP ? launch_gram_groups(ctx, kp, ctx->dxs, n, nullptr, n, 1, dK, ldk)
+                            : launch_gram_any(ctx, kp, ctx->dxs, n, nullptr, n, 1, dK, ldk);
     DISPATCH_D(launch_sym, ctx, kp, ctx->dxs, n, dK, ldk);
     LAUNCH_CHECK(ctx);
   } else {
     GPR_TRY(scale_inputs(ctx, kp, dXp, m, &ctx->dxps, &ctx->xps_cap));
     TimerScope ts(ctx, TC_OTHER, 0.0);
     if (gram_enabled(ctx, kp.d) && vec_store_ok(dK, ldk))
-      return launch_gram_any(ctx, kp, ctx->dxs, n, ctx->dxps, m, 0, dK, ldk);
+      return kp.nse > KMAXP ? launch_gram_groups(ctx, kp, ctx->dxs, n, ctx->dxps, m, 0, dK, ldk)
+                            : launch_gram_any(ctx, kp, ctx->dxs, n, ctx->dxps, m, 0, dK, ldk);
     DISPATCH_D(launch_cross, ctx, kp, ctx->dxs, n, ctx->dxps, m, dK, ldk);
     LAUNCH_CHECK(ctx);
   }
@@ -1281,7 +1568,8 @@ int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kp, const doubl
   ctx->kup_ptr = nullptr;
   // upper-only where the tile-DAG will take exactly this matrix directly (potrf_core), with
   // the Gram form (d <= 20) and one or two SE parts; the full symmetric K otherwise
-  const bool upper = ctx->kbuild_upper && n > 0 && gram_enabled(ctx, kp.d) && kp.nse <= 2 &&
+  const bool upper = ctx->kbuild_upper && n > 0 && gram_enabled(ctx, kp.d) &&
+                     kp.d <= GRAM_CT_MAXD && kp.nse <= 2 &&
                      dag_takes_whole(ctx, n, ldk, dK) && dag_shape_ok(n, ldk, dK);
   if (!upper) return launch_kernel_matrix(ctx, kp, dX, n, nullptr, n, 1, dK, ldk);
   GPR_TRY(scale_inputs(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));

@@ -8,25 +8,79 @@
 
 #include "../../include/gpr_hip.h"
 
-#define KMAXP 4   // max SquaredExp parts handled by the fused kernels
-#define KMAXD GPR_MAX_DIM
+#define KMAXP 4   // SquaredExp parts one fused-kernel launch handles (more: groups of KMAXP)
 
-// Kernel description passed BY VALUE to every assembly kernel (< 4 KB of kernargs).
+// Kernel description passed BY VALUE to every assembly kernel (a few dozen bytes of kernargs;
+// the per-part tables live in the context's parameter block, see KParBlock).
 // Mirrors split(hp, dims) of src/compose_covar.jl:21-28: the SE parts in `+` order
-// and the first WhiteNoise part (add_noise! src/compose_covar.jl:63-71).
+// and the first WhiteNoise part (add_noise! src/compose_covar.jl:63-71).  Any d >= 1 and any
+// number of parts, as the reference.
 struct KParams {
   int d;          // input dimension
-  int nse;        // number of SquaredExp parts (1..KMAXP)
+  int nse;        // number of SquaredExp parts (>= 1)
   int has_noise;  // a WhiteNoise part is present
-  int hp_off_noise;              // flat hp index of sigma_n (for the gradient)
   double eps;                    // jitter per SE part on a same-object diagonal
   double noise2;                 // sigma_n^2
   double noise_sigma;            // sigma_n
-  double sigma[KMAXP];           // sigma of each SE part
-  int hp_off[KMAXP];             // flat hp index of each SE part's sigma
-  double l[KMAXP][KMAXD];        // inverse length-scales (multipliers) per SE part
-  double l2[KMAXP][KMAXD];       // their squares (the gradient pass's distance)
+  double sigma[KMAXP];           // sigma of the first KMAXP SE parts -- of the launch's group of
+                                 // parts where a launcher narrows the description (kparams_group)
+  // device tables of ALL parts in this call's slot of the context's parameter block, filled in
+  // stream order by make_kparams: valid for launches on the context's streams until
+  // KParBlock::NSLOT further descriptions have been made on the context
+  const double* l;               // [nse][d] inverse length-scales (multipliers)
+  const double* l2;              // [nse][d] their squares (the gradient pass's distance)
+  const double* sig;             // [nse]    sigma of every SE part
   const double* exptab;          // device table 2^(j/256), j < 256 (ctx->dexptab)
+  // the caller's description (host; valid during the C call): sigma of any part via kp_sigma
+  const int* kinds;
+  int nk;
+  const double* hp;
+};
+
+// sigma of SE part p (host side, any p < nse)
+inline double kp_sigma(const KParams& kp, int p) {
+  int off = 0, se = 0;
+  for (int i = 0; i < kp.nk; ++i) {
+    if (kp.kinds[i] == GPR_SE) {
+      if (se++ == p) return kp.hp[off];
+      off += kp.d + 1;
+    } else {
+      off += 1;
+    }
+  }
+  return 0.0;
+}
+
+// The description narrowed to SE parts [p0, p0 + cnt) (cnt <= KMAXP) for one launch of the
+// fused kernels: sigma[] and the device tables start at part p0; has_noise as given.
+inline KParams kparams_group(const KParams& kp, int p0, int cnt, int has_noise) {
+  KParams g = kp;
+  g.nse = cnt;
+  g.has_noise = has_noise;
+  for (int p = 0; p < KMAXP; ++p) g.sigma[p] = p < cnt ? kp_sigma(kp, p0 + p) : 0.0;
+  g.l = kp.l + (size_t)p0 * kp.d;
+  g.l2 = kp.l2 + (size_t)p0 * kp.d;
+  g.sig = kp.sig + p0;
+  return g;
+}
+
+// Per-context parameter block: NSLOT device slots of `cap` doubles ([l | l2 | sigma] of one
+// kernel description each) and as many pinned host staging slots.  make_kparams fills host
+// slot `next`, uploads it in stream order and records ev[next] -- unless the tables equal those
+// of the description made last, whose slot then serves again; a slot is re-filled only once
+// its previous upload has completed (NSLOT descriptions later: the wait does not block in
+// practice, and no host synchronisation is added to a call).  `cap` starts at the largest
+// description of the old fixed-size envelope (4 parts x 64 dimensions) and grows on demand.
+struct KParBlock {
+  static constexpr int NSLOT = 8;
+  double* dev = nullptr;
+  double* host = nullptr;
+  size_t cap = 0;  // doubles per slot
+  int next = 0;
+  hipEvent_t ev[NSLOT] = {};
+  int last = -1;           // slot of the description made last (its host copy is compared), or -1
+  size_t last_need = 0;    // its length in doubles
+  std::vector<double> tmp; // the description being made
 };
 
 // TC_GEMM_PIPE is kernel-level (every launch of the pipelined 2-WG/CU GEMM, whatever its call
@@ -153,7 +207,7 @@ struct gpr_ctx {
   size_t gA_cap = 0;
   double* dgB = nullptr;        // Gram-assembly column operands
   size_t gB_cap = 0;
-  double* dgc = nullptr;        // Gram-assembly centres (KMAXP x KMAXD)
+  double* dgc = nullptr;        // Gram-assembly centres (nse x d)
   size_t gc_cap = 0;
   // upper-only K assembly for a factorisation (assembly.hip kmat_symu_kernel): its work list
   // (strip << 16 | segment, built once per n) and the matrix it last left without its strict
@@ -184,6 +238,9 @@ struct gpr_ctx {
   size_t tri_cap = 0;
   int kbuild_upper = 1;         // GPR_KBUILD_UPPER=0: fits build the full K (mirrored tiles)
   int kbuild_exact = 0;         // GPR_KBUILD_EXACT=1: the reference's difference form for K
+  int kbuild_gram_maxd = 1 << 30;  // GPR_KBUILD_GRAM_MAXD: largest d that takes the Gram form
+                                // (20: the compile-time-S kernels only, difference form above)
+  KParBlock kpar;               // kernel-description tables (make_kparams)
   int kbuild_colstore = 1;      // GPR_KBUILD_COLSTORE=0: single-part upper builds store in the
                                 // MFMA D layout instead of 1-KB column segments
   int cv_batch = 1;             // GPR_CV_BATCH=0: cv_batch folds one by one on child contexts

@@ -1,4 +1,5 @@
 // Context, memory, error and timing plumbing of libgpr_hip.so.
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -86,38 +87,92 @@ static void drain_timing(gpr_ctx* ctx) {
 // ---- kernel description ------------------------------------------------------------------
 int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d, double eps,
                  KParams* kp, int* D_total) {
-  if (!kinds || nk <= 0 || nk > GPR_MAX_PARTS) return set_err(ctx, GPR_E_ARG, "bad kinds/nk (%d)", nk);
+  if (!kinds || nk <= 0) return set_err(ctx, GPR_E_ARG, "bad kinds/nk (%d)", nk);
   if (!hp) return set_err(ctx, GPR_E_ARG, "hp is NULL");
-  if (d <= 0 || d > KMAXD) return set_err(ctx, GPR_E_UNSUP, "d=%d unsupported (1..%d)", d, KMAXD);
+  if (d <= 0) return set_err(ctx, GPR_E_ARG, "d=%d (needs d >= 1)", d);
   memset(kp, 0, sizeof *kp);
+  int nse = 0;
+  for (int i = 0; i < nk; ++i) {
+    if (kinds[i] == GPR_SE) ++nse;
+    else if (kinds[i] != GPR_WN) return set_err(ctx, GPR_E_ARG, "unknown kernel kind %d", kinds[i]);
+  }
+  if (nse == 0) return set_err(ctx, GPR_E_ARG, "kernel needs at least one SquaredExp part");
+  // this description's slot of the parameter block: [l (nse d) | l2 (nse d) | sigma (nse)]
+  KParBlock& kb = ctx->kpar;
+  const size_t nl = (size_t)nse * d, need = 2 * nl + nse;
+  if (need > kb.cap || !kb.dev) {
+    // (first use, or a description past every earlier one: never inside the 4 x 64 envelope
+    // once the block exists)
+    const size_t cap = std::max(need, (size_t)(2 * 4 * 64 + 4));
+    if (kb.dev) {
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, hipFree(kb.dev));
+      HIP_TRY(ctx, hipHostFree(kb.host));
+      kb.dev = kb.host = nullptr;
+      kb.cap = 0;
+    }
+    const size_t bytes = KParBlock::NSLOT * cap * sizeof(double);
+    if (hipMalloc((void**)&kb.dev, bytes) != hipSuccess) {
+      kb.dev = nullptr;
+      return set_err(ctx, GPR_E_NOMEM, "hipMalloc of %zu bytes failed", bytes);
+    }
+    if (hipHostMalloc((void**)&kb.host, bytes, hipHostMallocDefault) != hipSuccess) {
+      hipFree(kb.dev);
+      kb.dev = kb.host = nullptr;
+      return set_err(ctx, GPR_E_NOMEM, "hipHostMalloc of %zu bytes failed", bytes);
+    }
+    kb.cap = cap;
+    kb.last = -1;
+  }
+  kb.tmp.resize(need);
+  double* hl = kb.tmp.data();
   kp->exptab = ctx->dexptab;
   kp->d = d;
   kp->eps = eps;
+  kp->kinds = kinds;
+  kp->nk = nk;
+  kp->hp = hp;
   int off = 0;
   for (int i = 0; i < nk; ++i) {
     if (kinds[i] == GPR_SE) {
-      if (kp->nse >= KMAXP) return set_err(ctx, GPR_E_UNSUP, "more than %d SquaredExp parts", KMAXP);
-      kp->sigma[kp->nse] = hp[off];
-      kp->hp_off[kp->nse] = off;
+      if (kp->nse < KMAXP) kp->sigma[kp->nse] = hp[off];
+      hl[2 * nl + kp->nse] = hp[off];
       for (int k = 0; k < d; ++k) {
-        kp->l[kp->nse][k] = hp[off + 1 + k];
-        kp->l2[kp->nse][k] = hp[off + 1 + k] * hp[off + 1 + k];
+        hl[(size_t)kp->nse * d + k] = hp[off + 1 + k];
+        hl[nl + (size_t)kp->nse * d + k] = hp[off + 1 + k] * hp[off + 1 + k];
       }
       kp->nse++;
       off += d + 1;
-    } else if (kinds[i] == GPR_WN) {
+    } else {
       if (!kp->has_noise) {  // findfirst(WhiteNoise) -- src/compose_covar.jl:64-68
         kp->has_noise = 1;
         kp->noise_sigma = hp[off];
         kp->noise2 = hp[off] * hp[off];
-        kp->hp_off_noise = off;
       }
       off += 1;
-    } else {
-      return set_err(ctx, GPR_E_ARG, "unknown kernel kind %d", kinds[i]);
     }
   }
-  if (kp->nse == 0) return set_err(ctx, GPR_E_ARG, "kernel needs at least one SquaredExp part");
+  // the tables of the description made last on this context (a fit and the gradient or the
+  // posterior that follows it share hp): its slot serves again, nothing is uploaded
+  int slot = kb.last;
+  if (slot < 0 || kb.last_need != need ||
+      memcmp(kb.host + (size_t)slot * kb.cap, hl, need * sizeof(double)) != 0) {
+    slot = kb.next;
+    kb.next = (slot + 1) % KParBlock::NSLOT;
+    if (!kb.ev[slot]) HIP_TRY(ctx, hipEventCreateWithFlags(&kb.ev[slot], hipEventDisableTiming));
+    else HIP_TRY(ctx, hipEventSynchronize(kb.ev[slot]));  // this slot's previous upload (NSLOT ago)
+    kb.last = -1;
+    memcpy(kb.host + (size_t)slot * kb.cap, hl, need * sizeof(double));
+    HIP_TRY(ctx, hipMemcpyAsync(kb.dev + (size_t)slot * kb.cap, kb.host + (size_t)slot * kb.cap,
+                                need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(kb.ev[slot], ctx->stream));
+    kb.last = slot;
+    kb.last_need = need;
+  }
+  const double* dl = kb.dev + (size_t)slot * kb.cap;
+  kp->l = dl;
+  kp->l2 = dl + nl;
+  kp->sig = dl + 2 * nl;
   if (D_total) *D_total = off;
   return 0;
 }
@@ -146,6 +201,7 @@ const Knob kKnobs[] = {
     {"GPR_KBUILD_UPPER", &gpr_ctx::kbuild_upper, nullptr},
     {"GPR_KBUILD_EXACT", &gpr_ctx::kbuild_exact, nullptr},
     {"GPR_KBUILD_COLSTORE", &gpr_ctx::kbuild_colstore, nullptr},
+    {"GPR_KBUILD_GRAM_MAXD", &gpr_ctx::kbuild_gram_maxd, nullptr},
     {"GPR_CV_STREAMS", &gpr_ctx::cv_streams, nullptr},
     {"GPR_CV_BATCH", &gpr_ctx::cv_batch, nullptr},
     {"GPR_CV_BATCH_GB", nullptr, &gpr_ctx::cv_batch_gb},
@@ -278,6 +334,10 @@ int gpr_ctx_destroy(gpr_ctx_t ctx) {
   if (ctx->dgA) hipFree(ctx->dgA);
   if (ctx->dgB) hipFree(ctx->dgB);
   if (ctx->dgc) hipFree(ctx->dgc);
+  if (ctx->kpar.dev) hipFree(ctx->kpar.dev);
+  if (ctx->kpar.host) hipHostFree(ctx->kpar.host);
+  for (auto e : ctx->kpar.ev)
+    if (e) hipEventDestroy(e);
   for (auto& e : ctx->kup)
     if (e.d) hipFree(e.d);
   if (ctx->deig) hipFree(ctx->deig);

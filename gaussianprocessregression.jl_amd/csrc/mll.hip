@@ -73,8 +73,9 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
   const int i = i0 + lane;
   const bool irow = i < n;
   const double wgt = (bi == bj) ? 1.0 : 2.0;
-  for (int p = 0; p < kp.nse; ++p)
-    tabs[p][threadIdx.x] = (kp.sigma[p] * kp.sigma[p]) * kp.exptab[threadIdx.x];
+  // (the tables of the first KMAXP parts; further groups of KMAXP re-fill them below)
+  for (int p = 0; p < min(kp.nse, KMAXP); ++p)
+    tabs[p][threadIdx.x] = (kp.sig[p] * kp.sig[p]) * kp.exptab[threadIdx.x];
 
   // WhiteNoise term: alpha_a^2 - Kinv_aa from the thread whose columns hold a (diagonal tiles)
   const double ai = irow ? alpha[i] : 0.0;
@@ -88,7 +89,14 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
 
   int slot = 0;
   for (int p = 0; p < kp.nse; ++p) {
-    const double* ts = tabs[p];
+    if (p > 0 && (p & (KMAXP - 1)) == 0) {  // next group of parts: its exp tables
+      __syncthreads();
+      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)
+        tabs[g - p][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
+      __syncthreads();
+    }
+    const double* ts = tabs[p & (KMAXP - 1)];
+    const double* l2p = kp.l2 + (size_t)p * d;
     double acc_s = 0.0;
     double acc_l[D];
 #pragma unroll
@@ -116,7 +124,7 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
       for (int k = 0; k < D; ++k) {
         if (EXACT || k < d) {
           const double r = xr[k] - xc[k];
-          dpart[k & 3] = fma(kp.l2[p][k], r * r, dpart[k & 3]);
+          dpart[k & 3] = fma(l2p[k], r * r, dpart[k & 3]);
         }
       }
       const double dist = (dpart[0] + dpart[1]) + (dpart[2] + dpart[3]);
@@ -154,6 +162,130 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
   __syncthreads();
   if (threadIdx.x == 0)
     partial[(size_t)bid * nslot + slot] = red[0][D + 1] + red[1][D + 1] + red[2][D + 1] + red[3][D + 1];
+}
+
+// The same pass for d > 32, where the row point and its d sums no longer fit in registers.  Per
+// SE part and 64 x 64 tile, two phases:
+//  1. each thread's 16 weights mk_c = w (alpha_a alpha_b - Kinv_ab) K_p,ab, the distance by a
+//     run-time loop over all d (row point from global memory / L1, column point wave-uniform);
+//     the Kinv tile is read once per part; the 16 values go to the thread's own LDS slots (no
+//     barrier: each thread reads back only what it wrote) -- held in a register array they
+//     forced both column loops to be unrolled, and the unrolled wave-uniform point loads were
+//     hoisted into SGPRs and spilled (1686 SGPR spills);
+//  2. per chunk of GW = 32 dimensions: the row point's 32 features into registers, acc_l[k] +=
+//     mk_c (x_ka - x_kb)^2 over the 16 columns (column points re-read from L2, scalar loads),
+//     reduced as in mll_grad_tiles_kernel into slots 1 + 32 chunk + k.
+// S_sigma and the WhiteNoise slot are written once.  Same slot layout, same reduction kernel.
+constexpr int GW = 32;
+__global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const double* __restrict__ X,
+                                                            int n, const double* __restrict__ Kinv,
+                                                            size_t ldk, const double* __restrict__ alpha,
+                                                            double* __restrict__ partial, int nslot) {
+  __shared__ double red[4][GW + 2];
+  __shared__ double tabs[KMAXP][256];  // sigma_p^2 2^(j/256)
+  __shared__ double mks[16][256];      // mk_c of every thread
+  const int bid = blockIdx.x;
+  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
+  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
+  while (bj * (bj + 1) / 2 > bid) --bj;
+  const int bi = bid - bj * (bj + 1) / 2;
+  const int i0 = bi * GT, j0 = bj * GT;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int d = kp.d;
+  const int i = i0 + lane;
+  const bool irow = i < n;
+  const double wgt = (bi == bj) ? 1.0 : 2.0;
+  const size_t irc = (size_t)min(i, n - 1);
+  const double* xrow = X + irc * d;
+
+  const double ai = irow ? alpha[i] : 0.0;
+  double s_wn = 0.0;
+  if (bi == bj && irow && ((lane - wv) & 3) == 0) s_wn = ai * ai - Kinv[(size_t)i + (size_t)i * ldk];
+
+  int slot = 0;
+  for (int p = 0; p < kp.nse; ++p) {
+    if ((p & (KMAXP - 1)) == 0) {  // this group of parts' exp tables
+      __syncthreads();
+      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)
+        tabs[g - p][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
+      __syncthreads();
+    }
+    const double* ts = tabs[p & (KMAXP - 1)];
+    const double* l2p = kp.l2 + (size_t)p * d;
+    // phase 1: the 16 weights
+    double acc_s = 0.0;
+#pragma unroll 1
+    for (int c = 0; c < 16; ++c) {
+      const int jr = j0 + wv + 4 * c;
+      const int j = min(jr, n - 1);  // wave-uniform: scalar loads of the point
+      const double kin = Kinv[irc + (size_t)j * ldk];
+      const double mv = (irow && jr < n) ? wgt * (ai * alpha[j] - kin) : 0.0;
+      const double* xc = X + (size_t)j * d;
+      double dpart[4] = {0.0, 0.0, 0.0, 0.0};
+      int k = 0;
+#pragma unroll 1
+      for (; k + 4 <= d; k += 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const double r = xrow[k + u] - xc[k + u];
+          dpart[u] = fma(l2p[k + u], r * r, dpart[u]);
+        }
+      }
+      for (; k < d; ++k) {
+        const double r = xrow[k] - xc[k];
+        dpart[k & 3] = fma(l2p[k], r * r, dpart[k & 3]);
+      }
+      const double dist = (dpart[0] + dpart[1]) + (dpart[2] + dpart[3]);
+      const double Kp = kexp_s2(dist, ts) + (i == j ? kp.eps : 0.0);
+      const double mk = mv * Kp;
+      mks[c][threadIdx.x] = mk;
+      acc_s += mk;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
+    // phase 2: the length-scale sums, GW dimensions at a time
+    for (int k0 = 0; k0 < d; k0 += GW) {
+      const int kn = min(GW, d - k0);  // wave-uniform
+      double xr[GW], acc_l[GW];
+#pragma unroll
+      for (int k = 0; k < GW; ++k) {
+        xr[k] = k < kn ? xrow[k0 + k] : 0.0;
+        acc_l[k] = 0.0;
+      }
+#pragma unroll 1
+      for (int c = 0; c < 16; ++c) {
+        const int j = min(j0 + wv + 4 * c, n - 1);
+        const double* xc = X + (size_t)j * d + k0;
+        const double mk = mks[c][threadIdx.x];
+#pragma unroll
+        for (int k = 0; k < GW; ++k) {
+          const double r = xr[k] - (k < kn ? xc[k] : 0.0);
+          acc_l[k] = fma(mk, r * r, acc_l[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < GW; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc_l[k] += __shfl_xor(acc_l[k], o);
+      __syncthreads();
+      if (lane == 0) {
+        red[wv][0] = acc_s;
+#pragma unroll
+        for (int k = 0; k < GW; ++k) red[wv][1 + k] = acc_l[k];
+      }
+      __syncthreads();
+      // slot 0 of the part (S_sigma) with the first chunk, then this chunk's kn sums
+      for (int t = threadIdx.x + (k0 ? 1 : 0); t < kn + 1; t += 256)
+        partial[(size_t)bid * nslot + slot + (t ? k0 + t : 0)] =
+            red[0][t] + red[1][t] + red[2][t] + red[3][t];
+    }
+    slot += d + 1;
+  }
+  for (int o = 32; o > 0; o >>= 1) s_wn += __shfl_xor(s_wn, o);
+  __syncthreads();
+  if (lane == 0) red[wv][GW + 1] = s_wn;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partial[(size_t)bid * nslot + slot] = red[0][GW + 1] + red[1][GW + 1] + red[2][GW + 1] + red[3][GW + 1];
 }
 
 // out[slot] = sum_b partial[b][slot]  (fixed order)
@@ -208,7 +340,6 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   KParams kp;
   int D = 0;
   GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, &D));
-  if (d > 32) return set_err(ctx, GPR_E_UNSUP, "gpr_mll_grad supports d <= 32 (got %d)", d);
   if (n <= 0 || ldk < n || !dX || !dKinv || !dalpha || !grad) return set_err(ctx, GPR_E_ARG, "bad args");
   const int nt = (n + GT - 1) / GT;
   const long long nblk = (long long)nt * (nt + 1) / 2;
@@ -222,7 +353,12 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
     else if (d <= 4) GPR_TRY(launch_grad_tiles<4>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else if (d <= 8) GPR_TRY(launch_grad_tiles<8>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else if (d <= 16) GPR_TRY(launch_grad_tiles<16>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
-    else GPR_TRY(launch_grad_tiles<32>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
+    else if (d <= 32) GPR_TRY(launch_grad_tiles<32>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
+    else {
+      mll_grad_wide_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, dX, n, dKinv, (size_t)ldk,
+                                                                    dalpha, partial, nslot);
+      LAUNCH_CHECK(ctx);
+    }
   }
   reduce_partials_kernel<<<nslot, 256, 0, ctx->stream>>>(partial, (int)nblk, nslot, sums);
   LAUNCH_CHECK(ctx);

@@ -153,13 +153,16 @@ __host__ __device__ inline double erf_diff(double x, double y) {
 }
 
 // k1[j] = prefac * prod_i erf(l_i (a_i - x_ij), l_i (b_i - x_ij))  (antideriv!, :16-31)
-__global__ void antideriv_se_kernel(const double* __restrict__ X, int n, int d, KParams kp,
-                                    const double* __restrict__ ab, double prefac,
+// (abl: a | b | l, d doubles each)
+__global__ void antideriv_se_kernel(const double* __restrict__ X, int n, int d,
+                                    const double* __restrict__ abl, double prefac,
                                     double* __restrict__ k1) {
+  const double* ab = abl;
+  const double* ls = abl + 2 * (size_t)d;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     double v = 1.0;
     for (int i = 0; i < d; ++i) {
-      const double l = kp.l[0][i], x = X[(size_t)j * d + i];
+      const double l = ls[i], x = X[(size_t)j * d + i];
       v *= erf_diff(l * (ab[i] - x), l * (ab[d + i] - x));
     }
     k1[j] = v * prefac;
@@ -439,13 +442,10 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
 
 int gpr_antideriv_se(gpr_ctx_t ctx, int d, const double* hp, const double* dX, int n,
                      const double* a, const double* b, double* dk1, double* k2) {
-  if (d <= 0 || d > KMAXD || n <= 0 || !hp || !dX || !a || !b)
+  if (d <= 0 || n <= 0 || !hp || !dX || !a || !b)
     return set_err(ctx, GPR_E_ARG, "bad args");
   // hp[0] = sigma, hp[1..d] = l, whatever kernel they belong to (the reference indexes
   // md.params the same way, src/integrate.jl:19-22)
-  KParams kp{};
-  kp.d = d;
-  for (int i = 0; i < d; ++i) kp.l[0][i] = hp[1 + i];
   double prefac = hp[0] * hp[0] * std::pow(RT_PI_BY_2, d);
   double inv = 1.0;
   for (int i = 0; i < d; ++i) inv *= 1.0 / hp[1 + i];
@@ -456,18 +456,19 @@ int gpr_antideriv_se(gpr_ctx_t ctx, int d, const double* hp, const double* dX, i
     *k2 = i2 * hp[0] * hp[0];
   }
   if (!dk1) return 0;
-  GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, (size_t)2 * d + 2));
-  double hab[2 * KMAXD];
+  GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, (size_t)3 * d + 2));
+  std::vector<double> habl(3 * (size_t)d);  // a | b | l
   for (int i = 0; i < d; ++i) {
-    hab[i] = a[i];
-    hab[d + i] = b[i];
+    habl[i] = a[i];
+    habl[d + i] = b[i];
+    habl[2 * (size_t)d + i] = hp[1 + i];
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->dscratch, hab, sizeof(double) * 2 * d, hipMemcpyHostToDevice,
-                              ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->dscratch, habl.data(), sizeof(double) * habl.size(),
+                              hipMemcpyHostToDevice, ctx->stream));
   const int blocks = (int)std::min<long long>((n + 255) / 256, 4096);
-  antideriv_se_kernel<<<blocks, 256, 0, ctx->stream>>>(dX, n, d, kp, ctx->dscratch, prefac, dk1);
+  antideriv_se_kernel<<<blocks, 256, 0, ctx->stream>>>(dX, n, d, ctx->dscratch, prefac, dk1);
   LAUNCH_CHECK(ctx);
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // hab is a stack array
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // habl lives until here
   return 0;
 }
 
@@ -1309,7 +1310,7 @@ int gpr_split_factors(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
   GPR_TRY(launch_scale_inputs(ctx, kp, dXe, ne, xes));
   GPR_TRY(launch_scale_inputs(ctx, kp, dXq, nq, xqs));
   const int p = part;
-  const double s2 = kp.sigma[p] * kp.sigma[p];
+  const double s2 = kp_sigma(kp, p) * kp_sigma(kp, p);
   if (dA) GPR_TRY(launch_pair(ctx, 1, d, xes + (size_t)p * d * ne, ne, xqs + (size_t)p * d * nq, nq, 1.0, dA, 1, ne));
   if (dB) GPR_TRY(launch_pair(ctx, 0, d, xes + (size_t)p * d * ne, ne, xs + (size_t)p * d * ns, ns, 1.0, dB, 1, ne));
   if (dC) GPR_TRY(launch_pair(ctx, 2, d, xs + (size_t)p * d * ns, ns, xqs + (size_t)p * d * nq, nq, s2, dC, 1, ns));
@@ -1349,7 +1350,7 @@ static int split_prepare(gpr_ctx* ctx, const KParams& kp, int d, const double* d
   GPR_TRY(launch_scale_inputs(ctx, kp, dXq, nq, f->xqs));
   for (int p = 0; p < nse; ++p)  // C: sigma, SplitDistanceC(x, xq)
     GPR_TRY(launch_pair(ctx, 2, d, f->xs + (size_t)p * d * ns, ns, f->xqs + (size_t)p * d * nq, nq,
-                        kp.sigma[p] * kp.sigma[p], f->C + p * szC, 1, ns));
+                        kp_sigma(kp, p) * kp_sigma(kp, p), f->C + p * szC, 1, ns));
   return 0;
 }
 

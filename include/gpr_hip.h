@@ -44,10 +44,11 @@ extern "C" {
 #define GPR_E_ARG (-1)      /* bad argument (message names it)                      */
 #define GPR_E_HIP (-2)      /* HIP runtime error                                    */
 #define GPR_E_NOMEM (-3)    /* device allocation failed                             */
-#define GPR_E_UNSUP (-4)    /* unsupported configuration (e.g. d > GPR_MAX_DIM)      */
+#define GPR_E_UNSUP (-4)    /* unsupported configuration (e.g. an eigen-reduction size) */
 
-#define GPR_MAX_DIM 64      /* max input dimension d                               */
-#define GPR_MAX_PARTS 8     /* max kernel parts in a composed kernel                */
+/* Kernel descriptions (kinds, nk, hp, d) have the reference's envelope: any input dimension
+ * d >= 1 and any number of SquaredExp / WhiteNoise parts (src/covariance.jl:85-95,
+ * src/compose_covar.jl:9-28,47-61). */
 
 /* predict modes (src/predict.jl:14-25) */
 #define GPR_PREDICT_MEAN 0  /* predict_mean  src/predict.jl:6-12                     */
@@ -101,6 +102,9 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *   GPR_FUSE_KINV     -1  gpr_fit_kinv: Z (1) and Z^T Z (2) inside the factorisation (-1 = 2)
  *   GPR_KBUILD_UPPER   1  fits assemble only what dpotrf 'U' reads (the DAG mirrors the rest)
  *   GPR_KBUILD_EXACT   0  1: K by the reference's difference form instead of the Gram form
+ *   GPR_KBUILD_GRAM_MAXD 1073741824  largest input dimension d whose K takes the Gram form on
+ *                         FP64 MFMA (d <= 20: kernels compiled per ceil(d/4); above: the
+ *                         runtime-d tile); 20: the difference form for every d > 20
  *   GPR_KBUILD_COLSTORE 1 single-part (SE) upper builds store 1-KB column segments through LDS;
  *                         0: the MFMA D layout (4 columns x 128 B per store instruction)
  *   GPR_CV_BATCH       1  gpr_cv_batch: every fold in one batched launch; 0: per fold
@@ -193,7 +197,9 @@ int gpr_mll(gpr_ctx_t ctx, const double* dU, int n, int ldu, const double* dy,
 /* grad[D] (host) of the negative log-marginal-likelihood w.r.t. hp, fused over all D
  * hyper-parameters in one pass over the upper triangle of K^{-1} (never materialising
  * dK): g_i = -0.5 sum_ab (alpha_a alpha_b - Kinv_ab) dK_i,ab.  Replaces the grad! loop of
- * src/cost.jl:119-126 with src/loss_grad.jl:43-52 and src/deriv_covar.jl:20-32.
+ * src/cost.jl:119-126 with src/loss_grad.jl:43-52 and src/deriv_covar.jl:20-32.  Any d (d <= 32:
+ * the row point and its d sums in registers; above: per tile the 16 weights first, then the
+ * length-scale sums 32 dimensions at a time) and any number of parts.
  * log_scale != 0 applies G .*= hp (src/cost.jl:60-70). */
 int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                  const double* dX, int n, const double* dKinv, int ldk,
