@@ -21,9 +21,9 @@
 // suffices; a task accumulates row blocks as their tiles become final (k < min(colprog[i],
 // colprog[j])), so only its last row block waits for the previous row.
 //
-// Scheduling: one workgroup per CU (128 KB of LDS: four 32-KB DMA stages of the GEMM
-// pipeline, or the diagonal block), tasks claimed from an atomic ticket in a host-built
-// topological order (row i of A's tiles, then row i of B's tiles, for i = 0, 1, ...): every
+// Scheduling: one workgroup per CU (the CU's whole 160 KB of LDS: a ring of five 32-KB DMA
+// stages of the GEMM pipeline, or the diagonal block), tasks claimed from an atomic ticket in
+// a host-built topological order (row i of A's tiles, then row i of B's, i = 0, 1, ...): every
 // tile a task waits for belongs to an earlier ticket, i.e. to a workgroup that is already
 // running, so the grid cannot deadlock whatever the residency.  Every wait is bounded
 // (~seconds): on timeout the launch flags info = -1 and every task still publishes, so the
@@ -105,12 +105,15 @@ namespace {
 
 constexpr int DT = 128;                     // tile edge
 constexpr int DTK = 16;                     // K rows per pipeline stage
+// LDS stages.  5 (default): the ring, one barrier per TWO stages (dag_accum).  4: the earlier
+// loop, one barrier per stage, DMA three stages ahead -- kept selectable for A/B builds only.
 #ifndef DAG_DPB
-#define DAG_DPB 4
+#define DAG_DPB 5
 #endif
-constexpr int DPB = DAG_DPB;                // LDS stages (DMA DPB - 1 stages ahead)
+static_assert(DAG_DPB == 4 || DAG_DPB == 5, "dag_accum is written for 4 or 5 LDS stages");
+constexpr int DPB = DAG_DPB;
 constexpr int DSTAGE = (DT + DT) * DTK;     // doubles per stage (P image, then Q)
-constexpr int DLDS = DPB * DSTAGE;          // 16384 doubles = 128 KB at DPB = 4
+constexpr int DLDS = DPB * DSTAGE;          // 20480 doubles = 160 KB at DPB = 5
 // the task loop's three LDS ints: after the stages when they fit in the 160 KB, else in the
 // last stage's final 16 bytes -- they are live only between accumulations (every dag_accum
 // ends with a barrier after its last LDS read; the ints are read before the next one starts)
@@ -172,10 +175,22 @@ __device__ __forceinline__ int dag_idx(int row, int chunk) {
 // acc[i][j][r] += sum_{k < 16 nst} P[k + m ldp] Q[k + n ldq] for the tile element
 // (m, n) = (64 wm + 16 j + (lane & 15), 64 wn + 16 i + (lane >> 4) + 4 r)  (gemm.hip's layout:
 // the Q fragment is the MFMA A operand).  Rows m >= mv / n >= nv are clamped (their results
-// are never stored).  The pipelined gemm.hip body at one workgroup per CU: four LDS stages
-// fed by LDS-DMA (global_load_lds_dwordx4, swizzle applied on the source address), DMA three
-// stages ahead, next stage's fragments read during the current stage's MFMAs.  Leaves the
-// LDS free (ends with a barrier).
+// are never stored).  The pipelined gemm.hip body at one workgroup per CU: a ring of five LDS
+// stages fed by LDS-DMA (global_load_lds_dwordx4, swizzle applied on the source address), next
+// stage's fragments read during the current stage's MFMAs.  Leaves the LDS free (ends with a
+// barrier).
+//
+// ONE barrier per TWO stages.  Period p computes stages s = 2 p and s + 1; stage t lives in
+// buffer t % 5.  At the top of a period a wave has stage s's fragments in registers; it waits for
+// its own fragment reads (lgkmcnt) and for its own DMA of every stage but the youngest (vmcnt:
+// stages <= s + 2 landed, s + 3 in flight), then meets the others at the barrier.  Behind the
+// barrier stages s + 1 and s + 2 are complete for every wave and the buffers of stages s - 1
+// and s have been read by every wave, so the DMA of stages s + 4 and s + 5 goes into those two,
+// the first half reads stage s + 1's fragments under stage s's MFMAs, and the second half --
+// no barrier in between -- stage s + 2's under stage s + 1's.  Stage s + 4 has a whole period
+// (two stage times) to land before the next barrier, the lead the one-barrier-per-stage loop
+// gave its DMA; at most 24 pieces are outstanding per wave.  The MFMA order per accumulator is
+// k ascending in both loops, so the results are bit for bit the same.
 //
 // TRI (the W-products U_ij = W_i^T B, K = 128, P = W_i upper triangular: P[k + m ldp] = 0 for
 // k > m): stage s (k in [16 s, 16 s + 16)) only feeds the 16-row blocks mb >= s of the result,
@@ -205,8 +220,10 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
     srcP[r] = P + 2 * c + (size_t)min(row, mv - 1) * ldp;
     srcQ[r] = Q + 2 * c + (size_t)min(row, nv - 1) * ldq;
   }
-  auto issue = [&](int s) {
-    double* base = lds + (s % DPB) * DSTAGE;
+  // (stage s into / out of buffer b; stages past the last re-load the last one: the pieces a
+  // wave has in flight stay a fixed count per stage, and their data is never used)
+  auto issue = [&](int s, int b) {
+    double* base = lds + b * DSTAGE;
     const size_t ko = (size_t)min(s, nst - 1) * DTK;
 #pragma unroll
     for (int r = 0; r < DNDMA; ++r) {
@@ -214,8 +231,8 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
       __builtin_amdgcn_global_load_lds(srcQ[r] + ko, base + DT * DTK + (4 * r + w) * 128, 16, 0, 0);
     }
   };
-  auto read_frags = [&](d2 (&F)[DNP][8], int s) {
-    const double* ps = lds + (s % DPB) * DSTAGE;
+  auto read_frags = [&](d2 (&F)[DNP][8], int b) {
+    const double* ps = lds + b * DSTAGE;
     const double* qs = ps + DT * DTK;
 #pragma unroll
     for (int p = 0; p < DNP; ++p) {
@@ -244,6 +261,72 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
             acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(F[p][i][h], F[p][4 + j][h], acc[i][j], 0, 0, 0);
     }
   };
+#if DAG_DPB == 5
+  d2 F0[DNP][8], F1[DNP][8];
+  // buffer of stage s + k from b = s % 5 (k <= 5: one conditional subtract, scalar)
+  auto ring = [](int b, int k) { return b + k >= DPB ? b + k - DPB : b + k; };
+  // one period: stages s (fragments in F0) and s + 1; b = s % 5
+  auto period = [&](int s, int b) {
+    // keep the previous period's MFMAs ahead of this barrier: issued just before it, they run
+    // while the wave waits there (sunk past it, the matrix pipe idles through the wait)
+    __builtin_amdgcn_sched_barrier(0);
+    // own fragment reads of stages s - 1 and s retired before the barrier lets other waves' DMA
+    // overwrite those buffers (waited here, after the period's last MFMAs, not right behind them)
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // vmcnt(63) expcnt(7) lgkmcnt(0)
+    dag_vmcnt<DVM>();  // own DMA of stages <= s + 2 landed, s + 3 still in flight
+    __builtin_amdgcn_s_barrier();
+    issue(s + 4, ring(b, 4));  // stage s - 1's buffer
+    read_frags(F1, ring(b, 1));
+    mfma_stage(F0, s);
+    if constexpr (!TRI) {  // (TRI, variable MFMA counts: the compiler's own order)
+      // an MFMA first behind the barrier (its fragments are in registers), then per stage the
+      // DMA pieces two MFMAs apart and the fragment reads two MFMAs apart (same-box C3 launch,
+      // profiles/r07_dagprof_c3.txt: pieces one MFMA apart +0.7 to +1.0 ms, reads one apart
+      // +3.6 ms, all 16 pieces in the first half +13 ms)
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read (LDS-DMA)
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+#pragma unroll
+      for (int t = 0; t < 8 * DNP; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - 1 - 2 * DVM - 16 * DNP, 0);
+    }
+    // second half: no barrier -- stage s + 2 landed for every wave before this period's -- and
+    // no sched_barrier either: as one scheduling region the period keeps its address arithmetic
+    // in two bunches (split in two regions, or given slots of its own between the MFMAs, the
+    // C3 launch measured no faster than the one-barrier loop: profiles/r07_dagprof_c3.txt)
+    issue(s + 5, b);  // stage s's buffer
+    read_frags(F0, ring(b, 2));
+    mfma_stage(F1, s + 1);
+    if constexpr (!TRI) {
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+#pragma unroll
+      for (int t = 0; t < 8 * DNP; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - 2 * DVM - 16 * DNP, 0);
+    }
+  };
+#pragma unroll
+  for (int t = 0; t < DPB - 1; ++t) issue(t, t);
+  dag_vmcnt<DVM * (DPB - 2)>();  // stage 0 landed
+  __builtin_amdgcn_s_barrier();
+  read_frags(F0, 0);
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  int s = 0;
+  for (int b = 0; s + 1 < nst; s += 2, b = ring(b, 2)) period(s, b);
+  // (an odd count ends with a single-stage half period: its fragments are in F0)
+#else  // DAG_DPB == 4: one barrier per stage, DMA three stages ahead (A/B builds)
   auto step = [&](int s, d2 (&Fc)[DNP][8], d2 (&Fn)[DNP][8]) {
     // keep the previous stage's MFMAs ahead of this barrier: issued just before it, they run
     // while the wave waits there (sunk past it, the matrix pipe idles through the wait)
@@ -253,8 +336,8 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
     __builtin_amdgcn_s_waitcnt(0xC07F);  // vmcnt(63) expcnt(7) lgkmcnt(0)
     dag_vmcnt<DVM * (DPB - 3)>();  // own DMA of stage s+1 retired, s+2.. still in flight
     __builtin_amdgcn_s_barrier();
-    issue(s + DPB - 1);
-    read_frags(Fn, s + 1);
+    issue(s + DPB - 1, (s + DPB - 1) % DPB);
+    read_frags(Fn, (s + 1) % DPB);
     mfma_stage(Fc, s);
     if constexpr (TRI) return;  // (variable MFMA counts: the compiler's own order)
 // instruction order inside a stage (same-box C3 DAG launch, profiles/r02e_ab_dag_sched_
@@ -302,7 +385,7 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
   };
   d2 F0[DNP][8], F1[DNP][8];
 #pragma unroll
-  for (int t = 0; t < DPB - 1; ++t) issue(t);
+  for (int t = 0; t < DPB - 1; ++t) issue(t, t);
   dag_vmcnt<DVM * (DPB - 2)>();
   __builtin_amdgcn_s_barrier();
   read_frags(F0, 0);
@@ -312,6 +395,7 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
     step(s, F0, F1);
     step(s + 1, F1, F0);
   }
+#endif
   if (s < nst) mfma_stage(F0, s);
   dag_vmcnt<0>();
   __syncthreads();

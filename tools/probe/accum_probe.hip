@@ -4,9 +4,14 @@
 // TMR = 2: 8 waves over a 256 x 128 tile (2 waves per SIMD; Q shared by both row halves: 48 KB
 // of operands per 16-deep stage for twice the flops of a 32-KB 128 x 128 stage).
 // Answers: per-CU FP64 MFMA rate and HBM traffic per flop of the two shapes before the DAG
-// is restructured around either.   Usage: accum_probe [K] [reps]
+// is restructured around either.   Usage: accum_probe [K] [reps] [config] [mode] [warm seconds]
+// (warm seconds: back-to-back launches of the same kernel before the timed ones, so the rate and
+// the in-kernel clock -- s_memtime / s_memrealtime around the loop, median over the workgroups
+// of the last launch -- are those of a chip that has settled under the load)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -26,11 +31,13 @@ __device__ __forceinline__ void vmcnt() {
 
 // TMR: 128-row tiles of P (1 or 2); NW: waves (4 = one per SIMD, 8 = two); each wave owns
 // (128 TMR / (NW / 2)) rows x 64 columns; NSTG: LDS stages; DBUF: next stage's fragments read
-// into a second register set during the current stage's MFMAs.
-template <int TMR, int NW, int NSTG, bool DBUF>
+// into a second register set during the current stage's MFMAs.  RING (NSTG = 5, DBUF): ONE
+// barrier per two stages -- period p computes stages 2 p and 2 p + 1, DMA of stages 2 p + 4 and
+// 2 p + 5 issued behind its barrier (dag.hip's dag_accum at DAG_DPB = 5).
+template <int TMR, int NW, int NSTG, bool DBUF, bool RING = false>
 __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restrict__ M, size_t ld,
                                                           int ncolblk, int nst, int mode,
-                                                          double* out) {
+                                                          double* out, unsigned long long* clk) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass cannot instantiate the amdgcn builtins)
   constexpr int PR = DT * TMR;             // P rows (tile rows)
   constexpr int WR = NW / 2;               // wave row groups
@@ -79,8 +86,9 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
     const int row = DRPD * (NW * r + w) + lane / DNCH;
     srcQ[r] = Q + 2 * ((lane % DNCH) ^ swz(row)) + (size_t)row * ld;
   }
-  auto issue = [&](int s) {
-    double* base = lds + (s % NSTG) * DSTAGE;
+  // (stage s into / out of LDS buffer b)
+  auto issue_b = [&](int s, int b) {
+    double* base = lds + b * DSTAGE;
     const size_t ko = (size_t)(mode == 2 ? min(s, nst - 1) & 63 : min(s, nst - 1)) * DTK;
 #pragma unroll
     for (int r = 0; r < NDP; ++r)
@@ -89,8 +97,9 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
     for (int r = 0; r < NDQ; ++r)
       __builtin_amdgcn_global_load_lds(srcQ[r] + ko, base + PR * DTK + (NW * r + w) * 128, 16, 0, 0);
   };
-  auto read_frags = [&](d2 (&F)[DNP][NF], int s) {
-    const double* ps = lds + (s % NSTG) * DSTAGE;
+  auto issue = [&](int s) { issue_b(s, s % NSTG); };
+  auto read_frags_b = [&](d2 (&F)[DNP][NF], int b) {
+    const double* ps = lds + b * DSTAGE;
     const double* qs = ps + PR * DTK;
 #pragma unroll
     for (int p = 0; p < DNP; ++p) {
@@ -103,6 +112,7 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
         F[p][4 + j] = *reinterpret_cast<const d2*>(&ps[lidx(wm * 16 * RB + j * 16 + (lane & 15), ch)]);
     }
   };
+  auto read_frags = [&](d2 (&F)[DNP][NF], int s) { read_frags_b(F, s % NSTG); };
   auto mfma_stage = [&](const d2 (&F)[DNP][NF]) {
 #pragma unroll
     for (int p = 0; p < DNP; ++p)
@@ -133,9 +143,57 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
     }
   };
   d2 F0[DNP][NF], F1[DNP][NF];
+  const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
   for (int t = 0; t < NSTG - 1; ++t) issue(t);
-  if (DBUF) {
+  if constexpr (RING) {
+    static_assert(NSTG == 5 && DBUF, "the ring schedule is written for five buffers");
+    vmcnt<DVM * 3>();  // stage 0 landed (1, 2, 3 in flight)
+    __builtin_amdgcn_s_barrier();
+    read_frags_b(F0, 0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    // b: buffer of stage s (= s % 5, kept incrementally); F0 holds stage s's fragments
+    auto ring = [](int b, int k) { return b + k >= NSTG ? b + k - NSTG : b + k; };
+    auto period = [&](int s, int b) {
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // own reads of stages s - 1, s retired
+      vmcnt<DVM>();                         // own DMA of stages <= s + 2 landed, s + 3 in flight
+      __builtin_amdgcn_s_barrier();
+      issue_b(s + 4, ring(b, 4));  // stage s - 1's buffer
+      read_frags_b(F1, ring(b, 1));
+      mfma_stage(F0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // an MFMA first: F0 is in registers
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) {  // (DMA pieces two MFMAs apart, as dag.hip)
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+#pragma unroll
+      for (int t = 0; t < NDS; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, NMF - 1 - 2 * DVM - 2 * NDS, 0);
+      // second half, no barrier (stage s + 2 landed above) and one scheduling region with the first
+      issue_b(s + 5, b);            // stage s's buffer
+      read_frags_b(F0, ring(b, 2));
+      mfma_stage(F1);
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+#pragma unroll
+      for (int t = 0; t < NDS; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, NMF - 2 * DVM - 2 * NDS, 0);
+    };
+    int s = 0, b = 0;
+    for (; s + 1 < nst; s += 2, b = ring(b, 2)) period(s, b);
+    if (s < nst) mfma_stage(F0);
+  } else if (DBUF) {
     vmcnt<DVM * (NSTG - 2)>();
     __builtin_amdgcn_s_barrier();
     read_frags(F0, 0);
@@ -173,6 +231,12 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
   }
   vmcnt<0>();
   __syncthreads();
+  // the loop's clock: core-clock ticks per 100-MHz realtime tick, into a buffer of its own
+  const unsigned long long ck1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
+  if (tid == 0) {
+    clk[blockIdx.x * 2] = ck1 - ck0;
+    clk[blockIdx.x * 2 + 1] = rt1 - rt0;
+  }
   double t = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -332,40 +396,68 @@ void run_priv(const double* M, size_t ld, int ncolblk, int K, int reps, int mode
          PK, NSTG, lds / 1024, flops / ms / 1e9, flops / ms / 1e9 / cus, ms / reps);
 }
 
-template <int TMR, int NW, int NSTG, bool DBUF>
+static double g_warm_s = 0.0;  // back-to-back launches before the timed ones (seconds)
+
+template <int TMR, int NW, int NSTG, bool DBUF, bool RING = false>
 void run(const double* M, size_t ld, int ncolblk, int K, int reps, int mode, double* out, int cus) {
   constexpr size_t lds = sizeof(double) * NSTG * (DT * TMR + DT) * DTK;
-  auto kern = accum_kernel<TMR, NW, NSTG, DBUF>;
+  auto kern = accum_kernel<TMR, NW, NSTG, DBUF, RING>;
+  unsigned long long* clk = nullptr;
+  if (hipMalloc(&clk, sizeof(unsigned long long) * 2 * cus) != hipSuccess) return;
   if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
       hipSuccess) {
     printf("TMR=%d NW=%d NSTG=%d: cannot set %zu B of LDS\n", TMR, NW, NSTG, lds);
     return;
   }
   const int nst = K / DTK;
-  hipLaunchKernelGGL(kern, dim3(cus), dim3(NW * 64), lds, 0, M, ld, ncolblk, 8, mode, out);
+  hipLaunchKernelGGL(kern, dim3(cus), dim3(NW * 64), lds, 0, M, ld, ncolblk, 8, mode, out, clk);
   hipError_t le = hipGetLastError();
   if (le == hipSuccess) le = hipDeviceSynchronize();
   if (le != hipSuccess) {
     printf("TMR=%d NW=%d NSTG=%d: launch failed: %s\n", TMR, NW, NSTG, hipGetErrorString(le));
     return;
   }
+  // warm-up: batches of 8 launches, at most two batches queued, until g_warm_s has passed
+  if (g_warm_s > 0) {
+    const auto t0 = std::chrono::steady_clock::now();
+    hipEvent_t eb[2];
+    (void)hipEventCreate(&eb[0]);
+    (void)hipEventCreate(&eb[1]);
+    for (int it = 0; std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < g_warm_s; ++it) {
+      if (it >= 2 && hipEventSynchronize(eb[it & 1]) != hipSuccess) return;
+      for (int r = 0; r < 8; ++r)
+        hipLaunchKernelGGL(kern, dim3(cus), dim3(NW * 64), lds, 0, M, ld, ncolblk, nst, mode, out, clk);
+      (void)hipEventRecord(eb[it & 1]);
+    }
+  }
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
   (void)hipEventRecord(e0);
   for (int r = 0; r < reps; ++r)
-    hipLaunchKernelGGL(kern, dim3(cus), dim3(NW * 64), lds, 0, M, ld, ncolblk, nst, mode, out);
+    hipLaunchKernelGGL(kern, dim3(cus), dim3(NW * 64), lds, 0, M, ld, ncolblk, nst, mode, out, clk);
   (void)hipEventRecord(e1);
-  (void)hipEventSynchronize(e1);
+  if (hipEventSynchronize(e1) != hipSuccess) {
+    printf("TMR=%d NW=%d NSTG=%d: timed launches failed\n", TMR, NW, NSTG);
+    return;
+  }
   float ms;
   (void)hipEventElapsedTime(&ms, e0, e1);
+  std::vector<unsigned long long> hc(2 * (size_t)cus);
+  (void)hipMemcpy(hc.data(), clk, sizeof(unsigned long long) * hc.size(), hipMemcpyDeviceToHost);
+  std::vector<double> ghz(cus);
+  for (int c = 0; c < cus; ++c) ghz[c] = hc[2 * c + 1] ? 0.1 * (double)hc[2 * c] / (double)hc[2 * c + 1] : 0.0;
+  std::sort(ghz.begin(), ghz.end());
   const double flops = 2.0 * DT * TMR * DT * (double)nst * DTK * cus * reps;
   const double bytes = 8.0 * (DT * TMR + DT) * (double)nst * DTK * cus * reps;
-  printf("%s tile %3dx128, %d waves, %d stages (%3zu KB), %s fragments: %.2f TFLOP/s = %.4f per CU, "
-         "%.1f flop/B, operand stream %.2f TB/s (%.3f ms per launch)\n",
+  printf("%s tile %3dx128, %d waves, %d stages (%3zu KB), %s fragments%s: %.2f TFLOP/s = %.4f per CU, "
+         "%.1f flop/B, operand stream %.2f TB/s (%.3f ms per launch), in-kernel clock %.3f GHz "
+         "(median of %d workgroups, after %.1f s of launches)\n",
          mode == 1 ? "dag-like" : mode == 2 ? "L2-held " : "hot     ",
-         DT * TMR, NW, NSTG, lds / 1024, DBUF ? "2-set" : "1-set", flops / ms / 1e9,
-         flops / ms / 1e9 / cus, flops / bytes, bytes / ms / 1e9, ms / reps);
+         DT * TMR, NW, NSTG, lds / 1024, DBUF ? "2-set" : "1-set",
+         RING ? ", one barrier per two stages" : "", flops / ms / 1e9,
+         flops / ms / 1e9 / cus, flops / bytes, bytes / ms / 1e9, ms / reps, ghz[cus / 2], cus, g_warm_s);
+  (void)hipFree(clk);
 }
 
 int main(int argc, char** argv) {
@@ -385,6 +477,7 @@ int main(int argc, char** argv) {
   (void)hipMemcpy(M, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice);
   const int cfg = argc > 3 ? atoi(argv[3]) : 0;
   const int mode = argc > 4 ? atoi(argv[4]) : 0;
+  g_warm_s = argc > 5 ? atof(argv[5]) : 0.0;
   printf("K = %d, %d CUs, %d reps, config %d\n", K, cus, reps, cfg);
   switch (cfg) {
     case 0: run<1, 4, 4, true>(M, ld, ncolblk, K, reps, mode, out, cus); break;   // today's dag_accum
@@ -396,6 +489,7 @@ int main(int argc, char** argv) {
     case 6: run_priv<16, 2>(M, ld, ncolblk, K, reps, mode, out, cus); break;  // 128 KB
     case 7: run<1, 8, 4, true>(M, ld, ncolblk, K, reps, mode, out, cus); break;   // 128 x 128, 2 waves/SIMD (32 x 64 each)
     case 8: run<1, 8, 4, false>(M, ld, ncolblk, K, reps, mode, out, cus); break;
+    case 9: run<1, 4, 5, true, true>(M, ld, ncolblk, K, reps, mode, out, cus); break;  // ring of 5, barrier per 2 stages
   }
   return 0;
 }
