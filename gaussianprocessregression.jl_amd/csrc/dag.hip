@@ -31,9 +31,11 @@
 // depend on it) and the remaining tasks skip their arithmetic.
 //
 // Conditions (checked by the host): tiles of 128, n % 16 == 0, lda % 16 == 0 (and ldb),
-// 128-B aligned bases -- every 128-B line then belongs to exactly one tile.
+// 128-B aligned bases -- every 128-B line then belongs to exactly one tile; lda, ldb <= 2^25
+// (DAG_LD_MAX: the accumulation loop's 32-bit lane offsets).
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -105,13 +107,11 @@ namespace {
 
 constexpr int DT = 128;                     // tile edge
 constexpr int DTK = 16;                     // K rows per pipeline stage
-// LDS stages.  5 (default): the ring, one barrier per TWO stages (dag_accum).  4: the earlier
-// loop, one barrier per stage, DMA three stages ahead -- kept selectable for A/B builds only.
-#ifndef DAG_DPB
-#define DAG_DPB 5
-#endif
-static_assert(DAG_DPB == 4 || DAG_DPB == 5, "dag_accum is written for 4 or 5 LDS stages");
-constexpr int DPB = DAG_DPB;
+constexpr int DPB = 5;                      // LDS stages: the ring, one barrier per TWO stages (dag_accum)
+// Largest leading dimension (in doubles) the launch takes directly: dag_accum's 32-bit lane
+// offsets span 7 rows + 128 B, 56 ld + 128 < 2^31 bytes.  Anything beyond goes through the
+// padded copy (ld = n2 <= 128 * 32767, far below).
+constexpr int DAG_LD_MAX = 1 << 25;
 constexpr int DSTAGE = (DT + DT) * DTK;     // doubles per stage (P image, then Q)
 constexpr int DLDS = DPB * DSTAGE;          // 20480 doubles = 160 KB at DPB = 5
 // the task loop's three LDS ints: after the stages when they fit in the 160 KB, else in the
@@ -190,7 +190,7 @@ __device__ __forceinline__ int dag_idx(int row, int chunk) {
 // no barrier in between -- stage s + 2's under stage s + 1's.  Stage s + 4 has a whole period
 // (two stage times) to land before the next barrier, the lead the one-barrier-per-stage loop
 // gave its DMA; at most 24 pieces are outstanding per wave.  The MFMA order per accumulator is
-// k ascending in both loops, so the results are bit for bit the same.
+// k ascending in every version of the loop, so the results are bit for bit the same.
 //
 // TRI (the W-products U_ij = W_i^T B, K = 128, P = W_i upper triangular: P[k + m ldp] = 0 for
 // k > m): stage s (k in [16 s, 16 s + 16)) only feeds the 16-row blocks mb >= s of the result,
@@ -203,70 +203,175 @@ __device__ __forceinline__ int dag_mblk(int wm, int j) {
   return 4 * (j >> 1) + (wm ? 1 + (j & 1) : 3 * (j & 1));
 }
 
+// NO VECTOR-ALU ADDRESS ARITHMETIC IN THE LOOP.  Every address of a period is a wave-uniform
+// part plus a lane part that does not change inside a call, so the uniform part lives in SGPRs:
+//  - a DMA piece (8 rows of an operand) reads base + lane offset with the base an SGPR pair --
+//    the piece's first row (clamped to the last valid one) plus the stage's 128 B k, a scalar
+//    add -- and the lane offset a 32-bit VGPR computed once: swizzled chunk + (row within the
+//    piece, clamped) * ld * 8 < 56 ld + 128 bytes, exact (below 2^31) for ld <= DAG_LD_MAX.
+//    The compiler does not select this form of global_load_lds, so the piece is an asm statement
+//    (dag_dma16), which also writes the LDS destination to M0; vmcnt is kept by hand as before.
+//  - the ring position is a compile-time value: five periods (two laps of the ring) are unrolled,
+//    so a fragment read is a lane base (block p, 64-KB window k of the 160 KB: the DS immediate
+//    is 16 bits) plus an immediate -- 12 lane bases (18 for TRI) computed once per call.
+// The five-fold loop has ONE exit (whole groups of five periods), the 0..4 periods left over
+// follow behind plain if-thens: an exit between the unrolled periods made the compiler copy all
+// 128 accumulator registers on every exit edge.
+typedef __attribute__((address_space(3))) const char* dag_ldsp;
+
+// One 1-KB LDS-DMA piece, scalar-base form: lane source = sbase + voff, LDS destination = the
+// wave-uniform byte address lds_dst (through M0, written in the statement that reads it and
+// handed back as found) + 16 lane.  The compiler does not count it: callers keep vmcnt.
+__device__ __forceinline__ void dag_dma16(unsigned voff, const char* sbase, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_dst)
+      : "memory");
+}
+
+__device__ __forceinline__ const char* dag_uniform(const void* p) {
+  const unsigned long long v = (unsigned long long)(uintptr_t)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return reinterpret_cast<const char*>((uintptr_t)(((unsigned long long)hi << 32) | lo));
+}
+
 template <bool TRI = false>
 __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __restrict__ P,
                                           size_t ldp, int mv, const double* __restrict__ Q,
                                           size_t ldq, int nv, int nst, double* lds) {
   if (nst <= 0) return;
+  static_assert(DPB == 5 && DNDMA == 4 && DNP == 2, "the unrolled ring is written for this shape");
+  using std::integral_constant;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w & 1, wn = w >> 1;
-  const double* srcP[DNDMA];
-  const double* srcQ[DNDMA];
+  // DMA piece r of an operand: rows 8 (4 r + w) .. + 7 (rows >= mv / nv re-read the last valid
+  // one, inside the operand).  gP / gQ: the piece's first row, scalar; oP / oQ: the lane's byte
+  // offset from it
+  const char* gP[DNDMA];
+  const char* gQ[DNDMA];
+  unsigned oP[DNDMA], oQ[DNDMA];
 #pragma unroll
   for (int r = 0; r < DNDMA; ++r) {
-    const int row = DRPD * (4 * r + w) + lane / DNCH;
-    const int c = (lane % DNCH) ^ dag_swz(row);
-    srcP[r] = P + 2 * c + (size_t)min(row, mv - 1) * ldp;
-    srcQ[r] = Q + 2 * c + (size_t)min(row, nv - 1) * ldq;
+    const int row0 = DRPD * (4 * r + w), row = row0 + lane / DNCH;
+    const unsigned c16 = 16u * ((lane % DNCH) ^ dag_swz(row));
+    const int p0 = min(row0, mv - 1), q0 = min(row0, nv - 1);
+    gP[r] = dag_uniform(P + (size_t)p0 * ldp);
+    gQ[r] = dag_uniform(Q + (size_t)q0 * ldq);
+    oP[r] = c16 + (unsigned)(min(row, mv - 1) - p0) * (unsigned)(8 * ldp);
+    oQ[r] = c16 + (unsigned)(min(row, nv - 1) - q0) * (unsigned)(8 * ldq);
+    asm volatile("" : "+v"(oP[r]), "+v"(oQ[r]));
   }
-  // (stage s into / out of buffer b; stages past the last re-load the last one: the pieces a
-  // wave has in flight stay a fixed count per stage, and their data is never used)
-  auto issue = [&](int s, int b) {
-    double* base = lds + b * DSTAGE;
-    const size_t ko = (size_t)min(s, nst - 1) * DTK;
-#pragma unroll
-    for (int r = 0; r < DNDMA; ++r) {
-      __builtin_amdgcn_global_load_lds(srcP[r] + ko, base + (4 * r + w) * 128, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(srcQ[r] + ko, base + DT * DTK + (4 * r + w) * 128, 16, 0, 0);
-    }
+  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dag_ldsp)lds);
+  // piece t (P 0, Q 0, P 1, Q 1, ...) of stage s into buffer bb (stages past the last re-load
+  // the last one: the pieces a wave has in flight stay a fixed count per stage, and their data
+  // is never used)
+  auto piece = [&](int t, int s, int bb) __attribute__((always_inline)) {
+    const size_t ko = (size_t)min(s, nst - 1) * (DTK * 8);
+    const int r = t >> 1;
+    const unsigned dst = lds0 + bb * (DSTAGE * 8) + (t & 1) * (DT * DTK * 8) + (4 * r + w) * 1024;
+    if (t & 1)
+      dag_dma16(oQ[r], gQ[r] + ko, dst);
+    else
+      dag_dma16(oP[r], gP[r] + ko, dst);
   };
-  auto read_frags = [&](d2 (&F)[DNP][8], int b) {
-    const double* ps = lds + b * DSTAGE;
-    const double* qs = ps + DT * DTK;
+  // fragment reads.  Element (row 16 blk + (lane & 15), chunk (lane >> 4) + 4 p) of an operand's
+  // image sits at 2048 blk + a_p with a_p = a_0 ^ (64 p) (dag_idx; the swizzle depends on
+  // lane & 15 only).  Lane bases: qb / pb [p][k] = image + wave part + a_p + 64 KB * k; TRI's
+  // row blocks dag_mblk(wm, j) = 4 (j >> 1) + (per wm and j & 1), the latter in the base.
+  constexpr int NJP = TRI ? 2 : 1;
+  dag_ldsp qb[DNP][3], pb[DNP][NJP][3];
+  {
+    const int l15 = lane & 15;
+    const unsigned a0 = 8u * (unsigned)dag_idx(l15, lane >> 4);
 #pragma unroll
-    for (int p = 0; p < DNP; ++p) {
-      const int ch = (lane >> 4) + 4 * p;
+    for (int p = 0; p < DNP; ++p)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-        F[p][i] = *reinterpret_cast<const d2*>(&qs[dag_idx(wn * 64 + i * 16 + (lane & 15), ch)]);
+      for (int k = 0; k < 3; ++k) {
+        const unsigned ap = (a0 ^ (64u * p)) + 65536u * k;
+        qb[p][k] = (dag_ldsp)lds + DT * DTK * 8 + wn * (64 * DTK * 8) + ap;
+        asm volatile("" : "+v"(qb[p][k]));
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int mrow = TRI ? 16 * dag_mblk(wm, j) : wm * 64 + j * 16;
-        F[p][4 + j] = *reinterpret_cast<const d2*>(&ps[dag_idx(mrow + (lane & 15), ch)]);
+        for (int jp = 0; jp < NJP; ++jp) {
+          pb[p][jp][k] = (dag_ldsp)lds + (TRI ? 16 * DTK * 8 * (wm ? 1 + jp : 3 * jp) : wm * (64 * DTK * 8)) + ap;
+          asm volatile("" : "+v"(pb[p][jp][k]));
+        }
       }
-    }
+  }
+  typedef __attribute__((address_space(3))) const d2* ldsd2;
+  // read t (0..15: block p = t / 8, then the four Q and the four P fragments) of a stage out of
+  // buffer bb (compile-time)
+  auto rd = [&](d2 (&F)[DNP][8], int t, int bb) __attribute__((always_inline)) {
+    const int p = t >> 3, f = t & 7, j = f & 3;
+    const int win = (bb & 1) * (DSTAGE * 8);
+    if (f < 4)
+      F[p][f] = *reinterpret_cast<ldsd2>(qb[p][bb >> 1] + win + j * (16 * DTK * 8));
+    else if (TRI)
+      F[p][f] = *reinterpret_cast<ldsd2>(pb[p][j & (NJP - 1)][bb >> 1] + win + (j >> 1) * (64 * DTK * 8));
+    else
+      F[p][f] = *reinterpret_cast<ldsd2>(pb[p][0][bb >> 1] + win + j * (16 * DTK * 8));
   };
-  auto mfma_stage = [&](const d2 (&F)[DNP][8], int s) {
+  // MFMA t (0..63) of a stage: j outermost, k ascending per accumulator
+  auto mf = [&](const d2 (&F)[DNP][8], int t) __attribute__((always_inline)) {
+    const int j = t >> 4, p = (t >> 3) & 1, h = (t >> 2) & 1, i = t & 3;
+    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(F[p][i][h], F[p][4 + j][h], acc[i][j], 0, 0, 0);
+  };
+  auto mfma_stage = [&](const d2 (&F)[DNP][8], int s) __attribute__((always_inline)) {
     (void)s;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (TRI && dag_mblk(wm, j) < s) continue;  // (wave-uniform: W_i's zeros)
 #pragma unroll
-      for (int p = 0; p < DNP; ++p)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(F[p][i][h], F[p][4 + j][h], acc[i][j], 0, 0, 0);
+      for (int t = 16 * j; t < 16 * j + 16; ++t) mf(F, t);
     }
   };
-#if DAG_DPB == 5
+  // half a period: stage s's MFMAs (fragments Fc), the DMA of stage sd into buffer bd, the reads
+  // of buffer br into Fn.  The kept order (same-box C3 launch, profiles/r07_dagprof_c3.txt:
+  // pieces one MFMA apart +0.7 to +1.0 ms, reads one apart +3.6 ms, all 16 pieces in the first
+  // half +13 ms): LEAD MFMAs (one behind the barrier: its fragments are in registers), the DMA
+  // pieces two MFMAs apart, the fragment reads two MFMAs apart.  The asm pieces belong to no
+  // sched_group, so each sits in a scheduling region of its own with its two MFMAs.
+  auto half = [&](const d2 (&Fc)[DNP][8], d2 (&Fn)[DNP][8], int s, int sd, int bd, int br,
+                  auto leadc) __attribute__((always_inline)) {
+    constexpr int LEAD = decltype(leadc)::value;
+    if constexpr (TRI) {  // (variable MFMA counts: the compiler's own order)
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) piece(t, sd, bd);
+#pragma unroll
+      for (int t = 0; t < 8 * DNP; ++t) rd(Fn, t, br);
+      mfma_stage(Fc, s);
+    } else {
+      int m = 0;
+#pragma unroll
+      for (; m < LEAD; ++m) mf(Fc, m);
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) {
+        __builtin_amdgcn_sched_barrier(0);
+        piece(t, sd, bd);
+        mf(Fc, m++);
+        mf(Fc, m++);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < 8 * DNP; ++t) rd(Fn, t, br);
+#pragma unroll
+      for (; m < 32 * DNP; ++m) mf(Fc, m);
+#pragma unroll
+      for (int t = 0; t < 8 * DNP; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - LEAD - 2 * DVM - 16 * DNP, 0);
+    }
+  };
   d2 F0[DNP][8], F1[DNP][8];
-  // buffer of stage s + k from b = s % 5 (k <= 5: one conditional subtract, scalar)
-  auto ring = [](int b, int k) { return b + k >= DPB ? b + k - DPB : b + k; };
-  // one period: stages s (fragments in F0) and s + 1; b = s % 5
-  auto period = [&](int s, int b) {
+  int s = 0;
+  // one period: stages s (fragments in F0) and s + 1; bc: s % 5
+  auto period = [&](auto bc) __attribute__((always_inline)) {
+    constexpr int B = decltype(bc)::value;
     // keep the previous period's MFMAs ahead of this barrier: issued just before it, they run
     // while the wave waits there (sunk past it, the matrix pipe idles through the wait)
     __builtin_amdgcn_sched_barrier(0);
@@ -275,127 +380,35 @@ __device__ __forceinline__ void dag_accum(d4v (&acc)[4][4], const double* __rest
     __builtin_amdgcn_s_waitcnt(0xC07F);  // vmcnt(63) expcnt(7) lgkmcnt(0)
     dag_vmcnt<DVM>();  // own DMA of stages <= s + 2 landed, s + 3 still in flight
     __builtin_amdgcn_s_barrier();
-    issue(s + 4, ring(b, 4));  // stage s - 1's buffer
-    read_frags(F1, ring(b, 1));
-    mfma_stage(F0, s);
-    if constexpr (!TRI) {  // (TRI, variable MFMA counts: the compiler's own order)
-      // an MFMA first behind the barrier (its fragments are in registers), then per stage the
-      // DMA pieces two MFMAs apart and the fragment reads two MFMAs apart (same-box C3 launch,
-      // profiles/r07_dagprof_c3.txt: pieces one MFMA apart +0.7 to +1.0 ms, reads one apart
-      // +3.6 ms, all 16 pieces in the first half +13 ms)
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-#pragma unroll
-      for (int t = 0; t < DVM; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read (LDS-DMA)
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      }
-#pragma unroll
-      for (int t = 0; t < 8 * DNP; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - 1 - 2 * DVM - 16 * DNP, 0);
-    }
-    // second half: no barrier -- stage s + 2 landed for every wave before this period's -- and
-    // no sched_barrier either: as one scheduling region the period keeps its address arithmetic
-    // in two bunches (split in two regions, or given slots of its own between the MFMAs, the
-    // C3 launch measured no faster than the one-barrier loop: profiles/r07_dagprof_c3.txt)
-    issue(s + 5, b);  // stage s's buffer
-    read_frags(F0, ring(b, 2));
-    mfma_stage(F1, s + 1);
-    if constexpr (!TRI) {
-#pragma unroll
-      for (int t = 0; t < DVM; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      }
-#pragma unroll
-      for (int t = 0; t < 8 * DNP; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - 2 * DVM - 16 * DNP, 0);
-    }
+    // stage s + 4 into stage s - 1's buffer, stage s + 1's fragments under stage s's MFMAs
+    half(F0, F1, s, s + 4, (B + 4) % DPB, (B + 1) % DPB, integral_constant<int, 1>{});
+    // second half: no barrier -- stage s + 2 landed for every wave before this period's --;
+    // stage s + 5 into stage s's buffer
+    half(F1, F0, s + 1, s + 5, B, (B + 2) % DPB, integral_constant<int, 0>{});
+    s += 2;
   };
 #pragma unroll
-  for (int t = 0; t < DPB - 1; ++t) issue(t, t);
+  for (int t = 0; t < DPB - 1; ++t)
+#pragma unroll
+    for (int u = 0; u < DVM; ++u) piece(u, t, t);
   dag_vmcnt<DVM * (DPB - 2)>();  // stage 0 landed
   __builtin_amdgcn_s_barrier();
-  read_frags(F0, 0);
+#pragma unroll
+  for (int t = 0; t < 8 * DNP; ++t) rd(F0, t, 0);
   __builtin_amdgcn_s_waitcnt(0xC07F);
-  int s = 0;
-  for (int b = 0; s + 1 < nst; s += 2, b = ring(b, 2)) period(s, b);
-  // (an odd count ends with a single-stage half period: its fragments are in F0)
-#else  // DAG_DPB == 4: one barrier per stage, DMA three stages ahead (A/B builds)
-  auto step = [&](int s, d2 (&Fc)[DNP][8], d2 (&Fn)[DNP][8]) {
-    // keep the previous stage's MFMAs ahead of this barrier: issued just before it, they run
-    // while the wave waits there (sunk past it, the matrix pipe idles through the wait)
-    __builtin_amdgcn_sched_barrier(0);
-    // the previous step's fragment reads retired before the barrier lets other waves' DMA
-    // overwrite that stage (waited here, after the step's last MFMAs, not right behind them)
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // vmcnt(63) expcnt(7) lgkmcnt(0)
-    dag_vmcnt<DVM * (DPB - 3)>();  // own DMA of stage s+1 retired, s+2.. still in flight
-    __builtin_amdgcn_s_barrier();
-    issue(s + DPB - 1, (s + DPB - 1) % DPB);
-    read_frags(Fn, (s + 1) % DPB);
-    mfma_stage(Fc, s);
-    if constexpr (TRI) return;  // (variable MFMA counts: the compiler's own order)
-// instruction order inside a stage (same-box C3 DAG launch, profiles/r02e_ab_dag_sched_
-// variants.txt): 0 (default) 299.8 ms, 1 300.1, 2 313.6, 3 314.1
-#ifndef DAG_SCHED
-#define DAG_SCHED 0
-#endif
-#if DAG_SCHED == 0
-#pragma unroll
-    for (int t = 0; t < DVM; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read (LDS-DMA)
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-    }
-#pragma unroll
-    for (int t = 0; t < 8 * DNP; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - DVM - 16 * DNP, 0);
-#elif DAG_SCHED == 1  // DMA spread over twice as many MFMAs
-#pragma unroll
-    for (int t = 0; t < DVM; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < 8 * DNP; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - 2 * DVM - 16 * DNP, 0);
-#elif DAG_SCHED == 2  // fragment reads first, then the DMA
-#pragma unroll
-    for (int t = 0; t < 8 * DNP; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < DVM; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 32 * DNP - 2 * DVM - 8 * DNP, 0);
-#endif  // DAG_SCHED == 3: the compiler's own order
-  };
-  d2 F0[DNP][8], F1[DNP][8];
-#pragma unroll
-  for (int t = 0; t < DPB - 1; ++t) issue(t, t);
-  dag_vmcnt<DVM * (DPB - 2)>();
-  __builtin_amdgcn_s_barrier();
-  read_frags(F0, 0);
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  int s = 0;
-  for (; s + 1 < nst; s += 2) {
-    step(s, F0, F1);
-    step(s + 1, F1, F0);
+  int np = nst >> 1;
+  for (; np >= 5; np -= 5) {
+    period(integral_constant<int, 0>{});
+    period(integral_constant<int, 2>{});
+    period(integral_constant<int, 4>{});
+    period(integral_constant<int, 1>{});
+    period(integral_constant<int, 3>{});
   }
-#endif
+  if (np > 0) period(integral_constant<int, 0>{});
+  if (np > 1) period(integral_constant<int, 2>{});
+  if (np > 2) period(integral_constant<int, 4>{});
+  if (np > 3) period(integral_constant<int, 1>{});
+  // (an odd count ends with a single-stage half period: its fragments are in F0)
   if (s < nst) mfma_stage(F0, s);
   dag_vmcnt<0>();
   __syncthreads();
@@ -779,9 +792,16 @@ static long long dag_spin_limit(const gpr_ctx* ctx) {
 
 // The launch's own shape conditions: every 128-B line belongs to one tile (leading dimensions
 // multiples of 16 doubles, 128-B aligned bases) and every K range is a multiple of the 16-row
-// pipeline stage (n % 16 == 0).
+// pipeline stage (n % 16 == 0); leading dimensions up to DAG_LD_MAX (dag_accum's 32-bit lane
+// offsets).
 bool dag_shape_ok(int n, int lda, const double* dA) {
-  return n > 0 && n % 16 == 0 && lda % 16 == 0 && ((uintptr_t)dA & 127) == 0 && n <= DT * 32767;
+  return n > 0 && n % 16 == 0 && lda % 16 == 0 && lda <= DAG_LD_MAX && ((uintptr_t)dA & 127) == 0 &&
+         n <= DT * 32767;
+}
+
+// (tests: the predicate itself, host only)
+extern "C" int gpr_debug_dag_shape_ok(int n, int lda, unsigned long long addr) {
+  return dag_shape_ok(n, lda, reinterpret_cast<const double*>((uintptr_t)addr)) ? 1 : 0;
 }
 
 // true when potrf_core factors (n, lda, dA) as one tile-DAG launch: directly, or for any other
@@ -867,10 +887,11 @@ int launch_potrf_dag(gpr_ctx* ctx, double* dA, int n, int lda, double* dB, int n
   if ((solve || lower) && (!dB || kglob)) return 1;
   if (mirror && (solve || kglob)) return 1;
   if (gram && (!lower || !dG || ldg < n || nrhs != n)) return 1;
-  if (ctx->nb != DT || n <= 0 || n % 16 || lda % 16 || ((uintptr_t)dA & 127) || n > DT * 32767 ||
-      kglob % DT)
+  if (ctx->nb != DT || n <= 0 || n % 16 || lda % 16 || lda > DAG_LD_MAX || ((uintptr_t)dA & 127) ||
+      n > DT * 32767 || kglob % DT)
     return 1;
-  if (dB && (nrhs <= 0 || ldb % 16 || ((uintptr_t)dB & 127) || nrhs > DT * 65535)) return 1;
+  if (dB && (nrhs <= 0 || ldb % 16 || ldb > DAG_LD_MAX || ((uintptr_t)dB & 127) || nrhs > DT * 65535))
+    return 1;
   const int nt = (n + DT - 1) / DT, ntr = dB ? (nrhs + DT - 1) / DT : 0;
   GPR_TRY(ensure_winv(ctx, kglob + n, DT));
   if (ctx->dag_nt != nt || ctx->dag_ntr != ntr || ctx->dag_flags != (flags & ~DAG_MIRROR) ||
@@ -1023,9 +1044,11 @@ int launch_potrf_dag_batch(gpr_ctx* ctx, double* dA, size_t strA, int n, int lda
   hipStream_t st = ctx->stream;
   if (nbatch <= 0) return 0;
   // (its W slots are its own, so the context's inner block size does not matter)
-  if (n <= 0 || n % 16 || lda % 16 || strA % 16 || ((uintptr_t)dA & 127) || n > DT * 32767)
+  if (n <= 0 || n % 16 || lda % 16 || lda > DAG_LD_MAX || strA % 16 || ((uintptr_t)dA & 127) ||
+      n > DT * 32767)
     return 1;
-  if (dB && (nrhs <= 0 || ldb % 16 || strB % 16 || ((uintptr_t)dB & 127) || nrhs > DT * 65535))
+  if (dB && (nrhs <= 0 || ldb % 16 || ldb > DAG_LD_MAX || strB % 16 || ((uintptr_t)dB & 127) ||
+             nrhs > DT * 65535))
     return 1;
   const int nt = (n + DT - 1) / DT, ntr = dB ? (nrhs + DT - 1) / DT : 0;
   std::vector<unsigned> tasks;

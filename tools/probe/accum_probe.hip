@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 typedef double d4v __attribute__((ext_vector_type(4)));
@@ -29,12 +30,31 @@ __device__ __forceinline__ void vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
 }
 
+typedef __attribute__((address_space(3))) const char* ldsp;
+
+// One 1-KB LDS-DMA piece in the scalar-base form: lane source = sbase (SGPR pair) + voff (32-bit
+// VGPR byte offset), LDS destination = lds_dst (wave-uniform byte address, through M0) + 16 lane.
+// M0 is written in the statement that reads it and handed back as found.  Not counted by the
+// compiler: the caller keeps vmcnt.
+__device__ __forceinline__ void dma16_sbase(unsigned voff, const char* sbase, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_dst)
+      : "memory");
+}
+
 // TMR: 128-row tiles of P (1 or 2); NW: waves (4 = one per SIMD, 8 = two); each wave owns
 // (128 TMR / (NW / 2)) rows x 64 columns; NSTG: LDS stages; DBUF: next stage's fragments read
 // into a second register set during the current stage's MFMAs.  RING (NSTG = 5, DBUF): ONE
 // barrier per two stages -- period p computes stages 2 p and 2 p + 1, DMA of stages 2 p + 4 and
-// 2 p + 5 issued behind its barrier (dag.hip's dag_accum at DAG_DPB = 5).
-template <int TMR, int NW, int NSTG, bool DBUF, bool RING = false>
+// 2 p + 5 issued behind its barrier (dag.hip's dag_accum before round 8).  SBASE (RING): the same
+// schedule with no vector-ALU address arithmetic in the loop -- DMA sources are a scalar base per
+// 8-row piece plus a loop-invariant 32-bit lane offset, and five periods are unrolled so that the
+// ring position is a compile-time value and every fragment read is a loop-invariant lane base plus
+// an immediate.
+template <int TMR, int NW, int NSTG, bool DBUF, bool RING = false, bool SBASE = false>
 __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restrict__ M, size_t ld,
                                                           int ncolblk, int nst, int mode,
                                                           double* out, unsigned long long* clk) {
@@ -60,7 +80,10 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
   const int np_ = ncolblk - TMR - 1;
   // mode 2 (L2-resident): mode 0's operands, K wrapped at 1024 rows (64 stages): 2 MB of
   // operands per launch, held in every XCD's 4-MB L2 -- the same MFMA work with no HBM stream
-  const int pp = mode == 1 ? (b / 32) % np_ : 0, qp = mode == 1 ? TMR + (b % np_) : TMR;
+  // mode 3 (own panel): mode 1 with a Q panel of its own for EVERY workgroup (needs ncolblk >=
+  // workgroups + TMR; mode 1 at ncolblk = 64 wraps: four workgroups share each Q panel)
+  const int pp = mode == 1 || mode == 3 ? (b / 32) % np_ : 0;
+  const int qp = mode == 1 ? TMR + (b % np_) : mode == 3 ? TMR + b : TMR;
   const double* P = M + (size_t)pp * DT * ld;
   const double* Q = M + (size_t)qp * DT * ld;
   d4v acc[4][RB];
@@ -144,9 +167,126 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
   };
   d2 F0[DNP][NF], F1[DNP][NF];
   const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
+  if constexpr (RING && SBASE) {
+    static_assert(NSTG == 5 && DBUF && TMR == 1 && NW == 4, "written for dag_accum's shape");
+    // DMA piece r of an operand: rows 8 (4 r + w) .. + 7.  Scalar base: the piece's first row;
+    // lane offset: chunk (swizzled) + row within the piece -- < 7 * 8 ld + 128 bytes
+    const char* gP[NDP];
+    const char* gQ[NDQ];
+    unsigned oP[NDP], oQ[NDQ];
 #pragma unroll
-  for (int t = 0; t < NSTG - 1; ++t) issue(t);
-  if constexpr (RING) {
+    for (int r = 0; r < NDP; ++r) {
+      const int row0 = DRPD * (NW * r + w), rl = lane / DNCH;
+      const unsigned off = 16u * ((lane % DNCH) ^ swz(row0 + rl)) + (unsigned)rl * (unsigned)(8 * ld);
+      gP[r] = reinterpret_cast<const char*>(P + (size_t)row0 * ld);
+      gQ[r] = reinterpret_cast<const char*>(Q + (size_t)row0 * ld);
+      oP[r] = oQ[r] = off;
+      asm volatile("" : "+v"(oP[r]), "+v"(oQ[r]));
+    }
+    const unsigned lds0 = (unsigned)(uintptr_t)(ldsp)lds;
+    // piece t (0..7: P 0..3, then Q 0..3) of stage s into buffer bb
+    auto piece = [&](int t, int s, int bb) __attribute__((always_inline)) {
+      const size_t ko = (size_t)(mode == 2 ? min(s, nst - 1) & 63 : min(s, nst - 1)) * (DTK * 8);
+      const unsigned dst = lds0 + bb * (DSTAGE * 8) + (t >= NDP ? PR * DTK * 8 : 0) + (NW * (t % NDP) + w) * 1024;
+      if (t < NDP) dma16_sbase(oP[t], gP[t] + ko, dst);
+      else dma16_sbase(oQ[t - NDP], gQ[t - NDP] + ko, dst);
+    };
+    // fragment reads: lane bases (block p, 64-KB window k), then immediates only
+    ldsp qb[DNP][3], pb[DNP][3];
+    {
+      const int l15 = lane & 15;
+      const unsigned a0 = 8u * (l15 * DTK + ((((lane >> 4) ^ swz(l15))) << 1));
+#pragma unroll
+      for (int p = 0; p < DNP; ++p)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const unsigned ap = a0 ^ (64u * p);
+          qb[p][k] = (ldsp)lds + PR * DTK * 8 + wn * (64 * DTK * 8) + ap + k * 65536;
+          pb[p][k] = (ldsp)lds + wm * (64 * DTK * 8) + ap + k * 65536;
+          asm volatile("" : "+v"(qb[p][k]), "+v"(pb[p][k]));
+        }
+    }
+    typedef __attribute__((address_space(3))) const d2* ldsd2;
+    // read t (0..15) of a stage's fragments out of buffer bb (compile-time)
+    auto rd = [&](d2 (&F)[DNP][NF], int t, int bb) __attribute__((always_inline)) {
+      const int p = t / NF, f = t % NF;
+      const int imm = (bb & 1) * (DSTAGE * 8) + (f & 3) * (16 * DTK * 8);
+      F[p][f] = *reinterpret_cast<ldsd2>((f < 4 ? qb[p][bb >> 1] : pb[p][bb >> 1]) + imm);
+    };
+    auto mf = [&](const d2 (&F)[DNP][NF], int t) __attribute__((always_inline)) {  // MFMA t of a stage, mfma_stage's order
+      const int j = t % RB, i = (t / RB) % 4, h = (t / (4 * RB)) % 2, p = t / (8 * RB);
+      acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(F[p][i][h], F[p][4 + j][h], acc[i][j], 0, 0, 0);
+    };
+    // half a period: stage s's MFMAs (fragments Fc) with the DMA of stage sd into buffer bd two
+    // MFMAs apart behind LEAD MFMAs, then the reads of buffer br into Fn two MFMAs apart
+    auto half = [&](const d2 (&Fc)[DNP][NF], d2 (&Fn)[DNP][NF], int sd, int bd, int br, auto leadc) __attribute__((always_inline)) {
+      constexpr int lead = decltype(leadc)::value;
+      int m = 0;
+#pragma unroll
+      for (; m < lead; ++m) mf(Fc, m);
+#pragma unroll
+      for (int t = 0; t < DVM; ++t) {
+        __builtin_amdgcn_sched_barrier(0);
+        piece(t, sd, bd);
+        mf(Fc, m++);
+        mf(Fc, m++);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < NDS; ++t) rd(Fn, t, br);
+#pragma unroll
+      for (; m < NMF; ++m) mf(Fc, m);
+#pragma unroll
+      for (int t = 0; t < NDS; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, NMF - lead - 2 * DVM - 2 * NDS, 0);
+    };
+    auto period = [&](int s, auto bc) __attribute__((always_inline)) {  // stages s (in F0) and s + 1; bc: s % 5
+      constexpr int B = decltype(bc)::value;
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      vmcnt<DVM>();
+      __builtin_amdgcn_s_barrier();
+      half(F0, F1, s + 4, (B + 4) % NSTG, (B + 1) % NSTG, std::integral_constant<int, 1>{});
+      half(F1, F0, s + 5, B, (B + 2) % NSTG, std::integral_constant<int, 0>{});
+    };
+#pragma unroll
+    for (int t = 0; t < NSTG - 1; ++t)
+#pragma unroll
+      for (int u = 0; u < DVM; ++u) piece(u, t, t);
+    vmcnt<DVM * 3>();
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int t = 0; t < NDS; ++t) rd(F0, t, 0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    int s = 0;
+    auto per = [&](auto bc) __attribute__((always_inline)) {
+      period(s, bc);
+      s += 2;
+    };
+    using std::integral_constant;
+    // five periods are two laps of the ring: whole groups of five in the loop, then the 0..4
+    // periods that are left, each behind a check of its own (one loop exit and plain if-thens:
+    // with an exit between the unrolled periods the compiler copies all 128 accumulator
+    // registers at every exit edge)
+    int np = nst >> 1;
+    for (; np >= 5; np -= 5) {
+      per(integral_constant<int, 0>{});
+      per(integral_constant<int, 2>{});
+      per(integral_constant<int, 4>{});
+      per(integral_constant<int, 1>{});
+      per(integral_constant<int, 3>{});
+    }
+    if (np > 0) per(integral_constant<int, 0>{});
+    if (np > 1) per(integral_constant<int, 2>{});
+    if (np > 2) per(integral_constant<int, 4>{});
+    if (np > 3) per(integral_constant<int, 1>{});
+    if (s < nst) mfma_stage(F0);
+  } else if constexpr (RING) {
+#pragma unroll
+    for (int t = 0; t < NSTG - 1; ++t) issue(t);
     static_assert(NSTG == 5 && DBUF, "the ring schedule is written for five buffers");
     vmcnt<DVM * 3>();  // stage 0 landed (1, 2, 3 in flight)
     __builtin_amdgcn_s_barrier();
@@ -194,6 +334,8 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
     for (; s + 1 < nst; s += 2, b = ring(b, 2)) period(s, b);
     if (s < nst) mfma_stage(F0);
   } else if (DBUF) {
+#pragma unroll
+    for (int t = 0; t < NSTG - 1; ++t) issue(t);
     vmcnt<DVM * (NSTG - 2)>();
     __builtin_amdgcn_s_barrier();
     read_frags(F0, 0);
@@ -217,6 +359,8 @@ __global__ __launch_bounds__(NW * 64, 1) void accum_kernel(const double* __restr
   } else {
     // one fragment set: stage s's fragments read right after the barrier that makes it
     // complete (the other wave on the SIMD covers the LDS latency)
+#pragma unroll
+    for (int t = 0; t < NSTG - 1; ++t) issue(t);
     for (int s = 0; s < nst; ++s) {
       __builtin_amdgcn_sched_barrier(0);
       vmcnt<DVM * (NSTG - 2)>();
@@ -396,12 +540,17 @@ void run_priv(const double* M, size_t ld, int ncolblk, int K, int reps, int mode
          PK, NSTG, lds / 1024, flops / ms / 1e9, flops / ms / 1e9 / cus, ms / reps);
 }
 
+__global__ void fill_kernel(double* M, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    M[i] = (double)((i * 2654435761u) % 1000) * 1e-3;
+}
+
 static double g_warm_s = 0.0;  // back-to-back launches before the timed ones (seconds)
 
-template <int TMR, int NW, int NSTG, bool DBUF, bool RING = false>
+template <int TMR, int NW, int NSTG, bool DBUF, bool RING = false, bool SBASE = false>
 void run(const double* M, size_t ld, int ncolblk, int K, int reps, int mode, double* out, int cus) {
   constexpr size_t lds = sizeof(double) * NSTG * (DT * TMR + DT) * DTK;
-  auto kern = accum_kernel<TMR, NW, NSTG, DBUF, RING>;
+  auto kern = accum_kernel<TMR, NW, NSTG, DBUF, RING, SBASE>;
   unsigned long long* clk = nullptr;
   if (hipMalloc(&clk, sizeof(unsigned long long) * 2 * cus) != hipSuccess) return;
   if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
@@ -448,14 +597,21 @@ void run(const double* M, size_t ld, int ncolblk, int K, int reps, int mode, dou
   std::vector<double> ghz(cus);
   for (int c = 0; c < cus; ++c) ghz[c] = hc[2 * c + 1] ? 0.1 * (double)hc[2 * c] / (double)hc[2 * c + 1] : 0.0;
   std::sort(ghz.begin(), ghz.end());
+  // (the sums of the last launch: equal, bit for bit, between configs of one MFMA order)
+  std::vector<double> ho((size_t)cus * 512);
+  (void)hipMemcpy(ho.data(), out, sizeof(double) * ho.size(), hipMemcpyDeviceToHost);
+  double chk = 0;
+  for (int c = 0; c < cus; ++c)
+    for (int t = 0; t < NW * 64; ++t) chk += ho[(size_t)c * 512 + t];
+  printf("checksum %.17g\n", chk);
   const double flops = 2.0 * DT * TMR * DT * (double)nst * DTK * cus * reps;
   const double bytes = 8.0 * (DT * TMR + DT) * (double)nst * DTK * cus * reps;
   printf("%s tile %3dx128, %d waves, %d stages (%3zu KB), %s fragments%s: %.2f TFLOP/s = %.4f per CU, "
          "%.1f flop/B, operand stream %.2f TB/s (%.3f ms per launch), in-kernel clock %.3f GHz "
          "(median of %d workgroups, after %.1f s of launches)\n",
-         mode == 1 ? "dag-like" : mode == 2 ? "L2-held " : "hot     ",
+         mode == 1 ? "dag-like" : mode == 2 ? "L2-held " : mode == 3 ? "own-panel" : "hot     ",
          DT * TMR, NW, NSTG, lds / 1024, DBUF ? "2-set" : "1-set",
-         RING ? ", one barrier per two stages" : "", flops / ms / 1e9,
+         SBASE ? ", one barrier per two stages, scalar-addressed" : RING ? ", one barrier per two stages" : "", flops / ms / 1e9,
          flops / ms / 1e9 / cus, flops / bytes, bytes / ms / 1e9, ms / reps, ghz[cus / 2], cus, g_warm_s);
   (void)hipFree(clk);
 }
@@ -466,17 +622,20 @@ int main(int argc, char** argv) {
   hipDeviceProp_t p;
   (void)hipGetDeviceProperties(&p, 0);
   const int cus = p.multiProcessorCount;
-  const int ncolblk = 64;                         // 64 panels of 128 columns, K deep
+  const int cfg = argc > 3 ? atoi(argv[3]) : 0;
+  const int mode = argc > 4 ? atoi(argv[4]) : 0;
+  // 64 panels of 128 columns, K deep; mode 3: a Q panel per workgroup behind the P panels (at
+  // K = 32768 about 9 GB, so that every launch streams its operands from HBM)
+  const int ncolblk = mode == 3 ? cus + 9 : 64;
   const size_t ld = K, ncols = (size_t)ncolblk * DT;
   double *M, *out;
   if (hipMalloc(&M, sizeof(double) * ld * ncols) != hipSuccess ||
-      hipMalloc(&out, sizeof(double) * cus * 512) != hipSuccess)
+      hipMalloc(&out, sizeof(double) * cus * 512) != hipSuccess) {
+    printf("cannot allocate %zu MB\n", sizeof(double) * ld * ncols >> 20);
     return 1;
-  std::vector<double> h(ld * ncols);
-  for (size_t i = 0; i < h.size(); ++i) h[i] = (double)((i * 2654435761u) % 1000) * 1e-3;
-  (void)hipMemcpy(M, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice);
-  const int cfg = argc > 3 ? atoi(argv[3]) : 0;
-  const int mode = argc > 4 ? atoi(argv[4]) : 0;
+  }
+  hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, 0, M, ld * ncols);
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
   g_warm_s = argc > 5 ? atof(argv[5]) : 0.0;
   printf("K = %d, %d CUs, %d reps, config %d\n", K, cus, reps, cfg);
   switch (cfg) {
@@ -490,6 +649,7 @@ int main(int argc, char** argv) {
     case 7: run<1, 8, 4, true>(M, ld, ncolblk, K, reps, mode, out, cus); break;   // 128 x 128, 2 waves/SIMD (32 x 64 each)
     case 8: run<1, 8, 4, false>(M, ld, ncolblk, K, reps, mode, out, cus); break;
     case 9: run<1, 4, 5, true, true>(M, ld, ncolblk, K, reps, mode, out, cus); break;  // ring of 5, barrier per 2 stages
+    case 10: run<1, 4, 5, true, true, true>(M, ld, ncolblk, K, reps, mode, out, cus); break;  // + scalar-addressed (dag_accum)
   }
   return 0;
 }
