@@ -315,12 +315,19 @@ struct GemmArgs {
   int mask_off;           // column offset of C relative to its row origin (mask_upper)
   int kfrom_n;            // tile's K loop starts at its n0 (triangular factor, Z^T Z)
   int kend_from_m;        // tile's K loop ends at min(K, m0+TM) (upper-triangular P:
-                          // P[t][m] = 0 for t > m, e.g. P = U^{-1})
+                          // P[t][m] = 0 for t > m, e.g. P = U^{-1}); 2: at min(K, m0), the
+                          // rows above the diagonal tile only (its stages go to a tri_p launch)
   const double* qscale;   // optional per-k scale of Q (diag(wt) C)
   const double* E; int lde;  // optional Hadamard factor: C = beta*C + alpha*acc*E
   double* norm_out;       // optional: norm_out[n] -= sum_m (result)^2 (needs M <= tile)
   const int* info;        // optional: skip when *info != 0
   int occ1;               // launch at one workgroup per CU (lookahead co-residence)
+  // P is a factor BUFFER (upper triangle U, anything -- K, NaN -- below it): elements k > m
+  // are replaced by zero as the diagonal tile's K-stages are staged (a select, never a
+  // product).  Needs kend_from_m; default off.  (sample.hip: S = mu 1^T + U^T Z)
+  int tri_p;
+  int kfrom_m;            // with tri_p: the K loop starts at the tile's m0 (diagonal tile only)
+  const double* mu;       // with tri_p: optional, C[m, n] += mu[m] after alpha / beta
 };
 int launch_gemm_tn(gpr_ctx* ctx, const GemmArgs& g, int timing_class);
 

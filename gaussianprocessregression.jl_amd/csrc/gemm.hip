@@ -7,6 +7,7 @@
 //   * TRSM trailing update  B_c -= U_bc^T X_b
 //   * K^{-1} = Z^T Z        (Z = U^{-T}; upper tiles, K-range from the tile's n0)
 //   * split mean            mu = A o (B^T . diag(wt) C)   (Hadamard epilogue, qscale)
+//   * GP draws              S = mu 1^T + U^T Z            (P = a factor buffer, masked: tri_p)
 // so a single kernel with a few epilogue switches covers them all.
 //
 // v_mfma_f64_16x16x4_f64: lane l supplies A[l&15][k=l>>4] and B[k=l>>4][l&15] (one f64
@@ -111,6 +112,8 @@ __device__ __forceinline__ bool tile_coords(const GemmK& a, int& m0, int& n0) {
 }
 
 // C = alpha * acc (o E) + beta * C on the tile, optional column sum-of-squares into norm_out.
+// MU (the tri_p launches only): + mu[m] when g.mu is given.
+template <bool MU = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, d4 (&acc)[4][4], int m0, int n0,
                                               double* red, bool preloaded = false) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -135,6 +138,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, d4 (&acc)[4][4]
         if (has_e) v = v * (in ? Ep[(size_t)m + (size_t)n * g.lde] : 0.0);
         v = g.alpha * v;
         if (has_beta) v = v + g.beta * (in ? Cp[(size_t)m + (size_t)n * g.ldc] : 0.0);
+        if constexpr (MU) {
+          if (g.mu) v = v + (in ? g.mu[m] : 0.0);
+        }
         acc[i][j][r] = v;
       }
     }
@@ -172,7 +178,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, d4 (&acc)[4][4]
   }
 }
 
-template <bool VEC>
+// TRI (g.tri_p): P is a factor buffer whose strict lower triangle holds anything; the stages
+// of the diagonal tile (k0 >= m0) zero P[k][m] for k > m by a select when they are staged.
+template <bool VEC, bool TRI = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmK a) {
   const GemmArgs& g = a.g;
   if (g.info && *g.info != 0) return;
@@ -185,8 +193,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmK a) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w & 1, wn = w >> 1;
 
-  const int kbeg = g.kfrom_n ? n0 : 0;
-  const int kend = g.kend_from_m ? min(g.K, m0 + TM) : g.K;
+  const int kbeg = g.kfrom_n ? n0 : (TRI && g.kfrom_m ? m0 : 0);
+  const int kend = g.kend_from_m ? min(g.K, m0 + (g.kend_from_m == 2 ? 0 : TM)) : g.K;
   const int nst = kend > kbeg ? (kend - kbeg + TK - 1) / TK : 0;
 
   d4 acc[4][4];
@@ -224,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmK a) {
         const int k = k0 + kk;
         const bool kin = k < kend;
         const int m = m0 + col, n = n0 + col;
-        rp[r] = (kin && m < g.M) ? g.P[(size_t)k + (size_t)m * g.ldp] : 0.0;
+        rp[r] = (kin && m < g.M && (!TRI || k <= m)) ? g.P[(size_t)k + (size_t)m * g.ldp] : 0.0;
         double q = (kin && n < g.N) ? g.Q[(size_t)k + (size_t)n * g.ldq] : 0.0;
         if (g.qscale) q *= (kin ? g.qscale[k] : 0.0);
         rq[r] = q;
@@ -240,6 +248,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmK a) {
         const int col = idx >> 3, kp = idx & 7;
         const bool kin = k0 + 2 * kp < kend;
         const d2 z = {0.0, 0.0};
+        if constexpr (TRI) {
+          if (k0 + TK > m0) {  // a stage of the diagonal tile: keep k <= m only
+            const int k = k0 + 2 * kp, m = m0 + col;
+            vp[r][0] = k <= m ? vp[r][0] : 0.0;
+            vp[r][1] = k + 1 <= m ? vp[r][1] : 0.0;
+          }
+        }
         *reinterpret_cast<d2*>(&Ps[buf][lds_idx(col, kp)]) = (kin && m0 + col < g.M) ? vp[r] : z;
         *reinterpret_cast<d2*>(&Qs[buf][lds_idx(col, kp)]) = (kin && n0 + col < g.N) ? vq[r] : z;
       }
@@ -288,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmK a) {
     __syncthreads();
   }
 
-  gemm_epilogue(g, acc, m0, n0, &red[0][0]);
+  gemm_epilogue<TRI>(g, acc, m0, n0, &red[0][0]);
 }
 
 // ---- deep-pipelined variant: one workgroup per CU, four LDS stages fed by LDS-DMA ------
@@ -350,7 +365,8 @@ __device__ __forceinline__ void gemm_tn_pipe_body(const GemmK& a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w & 1, wn = w >> 1;
   const int kbeg = g.kfrom_n ? n0 : 0;
-  const int nst = ((g.kend_from_m ? min(g.K, m0 + TM) : g.K) - kbeg) / TKS;
+  const int nst =
+      ((g.kend_from_m ? min(g.K, m0 + (g.kend_from_m == 2 ? 0 : TM)) : g.K) - kbeg) / TKS;
 
   // DMA sources: instruction r of wave w fills rows ROWS_PER_DMA (4r + w) + (L / NCH); lane
   // L lands at physical chunk L % NCH of its row, so it fetches the logical chunk
@@ -509,7 +525,7 @@ __global__ __launch_bounds__(256, 4) void gemm_tn_narrow_kernel(GemmK a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kbeg = g.kfrom_n ? n0 : 0;
-  const int kend = g.kend_from_m ? min(g.K, m0 + TM) : g.K;
+  const int kend = g.kend_from_m ? min(g.K, m0 + (g.kend_from_m == 2 ? 0 : TM)) : g.K;
   const int nst = kend > kbeg ? (kend - kbeg + TK - 1) / TK : 0;
   d4 acc[2][2];
 #pragma unroll
@@ -611,6 +627,10 @@ __global__ __launch_bounds__(256, 4) void gemm_tn_narrow_kernel(GemmK a) {
 int launch_gemm_tn(gpr_ctx* ctx, const GemmArgs& g, int timing_class) {
   if (g.M <= 0 || g.N <= 0) return 0;
   if (g.norm_out && g.M > TM) return set_err(ctx, GPR_E_ARG, "gemm norm epilogue needs M<=%d", TM);
+  if (g.tri_p && (!g.kend_from_m || g.kend_from_m == 2 || g.upper || g.mask_upper || g.kfrom_n ||
+                  g.qscale || g.E || g.norm_out || g.occ1))
+    return set_err(ctx, GPR_E_ARG, "gemm tri_p: a plain kend_from_m product only");
+  if ((g.kfrom_m || g.mu) && !g.tri_p) return set_err(ctx, GPR_E_ARG, "gemm kfrom_m / mu need tri_p");
   GemmK a;
   a.g = g;
   a.tiles_m = (g.M + TM - 1) / TM;
@@ -637,6 +657,7 @@ int launch_gemm_tn(gpr_ctx* ctx, const GemmArgs& g, int timing_class) {
     flops = 2.0 * g.M * (double)g.N * g.K;
     if (g.kend_from_m)  // upper-triangular P: row m of the product uses K-range [0, m]
       flops = (double)g.N * g.M * (g.M + 1);
+    if (g.kend_from_m == 2 || g.kfrom_m) flops = 0.0;  // (two halves of one product: its caller counts)
     if (g.mask_upper) {  // exclude the masked corner rows m > n + mask_off
       const double rows_below = std::max(0.0, (double)g.M - g.mask_off);
       const double cut = std::min(rows_below, (double)g.N);
@@ -653,6 +674,12 @@ int launch_gemm_tn(gpr_ctx* ctx, const GemmArgs& g, int timing_class) {
   // multiple of TN).  Few 128 x 128 tiles at short K: the narrow-tile kernel spreads them
   // over 4x the CUs (up to 384 tiles)
   constexpr int narrow_max = 384;
+  if (g.tri_p) {  // the masked stages exist in the register-staged kernel only
+    if (vec) gemm_tn_kernel<true, true><<<(unsigned)nblk, 256, 0, ctx->ls>>>(a);
+    else gemm_tn_kernel<false, true><<<(unsigned)nblk, 256, 0, ctx->ls>>>(a);
+    LAUNCH_CHECK(ctx);
+    return 0;
+  }
   if (vec && !g.occ1 && !g.E && !g.norm_out && g.K <= 256 && nblk <= narrow_max &&
       !(g.upper && g.kfrom_n)) {
     GemmK an = a;

@@ -49,6 +49,7 @@ from .core import (
 )
 
 from .crossval import ChiSq, Mahalanobis, MSE, cv_batch, cv_step, cv_step_, kfoldcv
+from .distributions import GaussianProcess, NormalDistribution, sample, sample_posterior
 from .integrate import antideriv, antideriv2, erf_integ, gauss_integ, integrate
 from .train import (
     BFGS,

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from ctypes import POINTER, c_double, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, c_double, c_int, c_longlong, c_size_t, c_uint64, c_void_p
 
 import torch  # noqa: F401  (load torch's HIP runtime before ours)
 
@@ -102,6 +102,11 @@ _SIGS = {
     "gpr_split_predict_mgpu": (_i, [_p, _ip, _i, _dp, _i, _dp, _i, _dp, _dp, _i, _dp, _i, _i, _i, _d,
                                     _i, _dp, _dp, _ip]),
     "gpr_split_factors": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p]),
+    "gpr_randn": (_i, [_p, c_uint64, c_uint64, _p, c_size_t]),
+    "gpr_mvn_sample": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _p, _i]),
+    "gpr_mvn_factor": (_i, [_p, _p, _i, _i, _d, _ip]),
+    "gpr_sample_prior": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _d, _d, _p, _i, _i, _p, _i, _p, _i,
+                              _ip]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

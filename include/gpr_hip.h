@@ -254,6 +254,46 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
                     double* dK, int ldk, double* dalpha, const double* dXp, int m, int mode,
                     double* dmu, double* dvar, int ldv, double* dwork, int* info);
 
+/* ---- sampling: NormalDistribution / GaussianProcess / sample (src/distributions.jl) ---- */
+/* dZ[i] = element (offset + i) of the standard-normal stream of `seed`, i < count.  In place
+ * of randn(rng, dim) (src/distributions.jl:27); Julia's Xoshiro / ziggurat stream is NOT
+ * reproduced: a caller who needs the reference's numbers uploads its own z.  The stream is
+ * counter-based, so an element depends on (seed, offset + i) alone, never on how a range is
+ * cut into calls: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ * 0xBB67AE85), counter (lo32(g >> 1), hi32(g >> 1), 0, 0) and key (lo32(seed), hi32(seed)) for
+ * global index g; from the output words w0..w3, u1 = (((w1 << 32 | w0) >> 11) + 0.5) 2^-53, u2
+ * likewise from (w3, w2), r = sqrt(-2 ln u1); element g = r cos(2 pi u2) for even g,
+ * r sin(2 pi u2) for odd g.  Asynchronous. */
+int gpr_randn(gpr_ctx_t ctx, uint64_t seed, uint64_t offset, double* dZ, size_t count);
+
+/* S (n x ns, lds) = mu 1^T + U^T Z: s .= N.Sigma_ch.L * s .+ N.mu (src/distributions.jl:28) for
+ * ns draws at once.  U = the upper triangle of the factor buffer dU (n x n, ldu; from
+ * gpr_potrf_upper, gpr_fit, gpr_mvn_factor, ...): whatever lies below its diagonal -- K after a
+ * fit -- is masked while the diagonal tiles are staged, never multiplied (a NaN there does not
+ * reach S), and row tile t of the product reads k < min(n, 128 (t + 1)) only.  Z: n x ns (ldz);
+ * dmu: device n-vector or NULL (zeros).  FP64 MFMA; any n, ns >= 1, ldu, ldz, lds >= n.  dS
+ * overlapping dZ, dU or dmu: GPR_E_ARG.  Asynchronous. */
+int gpr_mvn_sample(gpr_ctx_t ctx, const double* dU, int n, int ldu, const double* dmu,
+                   const double* dZ, int ns, int ldz, double* dS, int lds);
+
+/* NormalDistribution(mu, Sigma) (src/distributions.jl:20-23): Sigma_ch = cholesky(Sigma .+ 1e-7),
+ * the shift added to EVERY element of the matrix that is factored, not to its diagonal.  dA
+ * (n x n, lda) holds the symmetric Sigma; on return its upper triangle holds U with
+ * U^T U = Sigma .+ shift, its strict lower triangle is untouched.  Returns *info > 0 (the order
+ * of the failing minor, PosDefException) otherwise 0; synchronises for info. */
+int gpr_mvn_factor(gpr_ctx_t ctx, double* dA, int n, int lda, double shift, int* info);
+
+/* sample(gp(x, hp)) (src/distributions.jl:33,41-45 + :20-30) in one call: K = kernel!(K, cov,
+ * hp, x) (the GPR_SELF form: eps per SE part + noise) into dK, K .+= shift, dpotrf 'U' in
+ * place, S = mu 1^T + U^T Z (dmu = f_mu.(eachcol(x)) or NULL; Z n x ns, ldz; S n x ns, lds).  dK
+ * ends as gpr_fit leaves it -- U in the upper triangle, the factored matrix (K .+ shift) in the
+ * strict lower one -- and serves gpr_mvn_sample for further draws.  Returns *info > 0 for a
+ * non-PD matrix (nothing is written to dS then); synchronises for info. */
+int gpr_sample_prior(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                     const double* dX, int n, const double* dmu, double shift, double eps,
+                     const double* dZ, int ns, int ldz, double* dK, int ldk, double* dS, int lds,
+                     int* info);
+
 /* ---- 8(f) rank 3: Bayesian quadrature of the posterior (src/integrate.jl) ------------- */
 /* antideriv!(k1, SquaredExp(), x, hp, a, b) and antideriv2 (src/integrate.jl:16-46): dk1[n]
  * = sigma^2 (sqrt(pi)/2)^d prod(1/l) prod_i erf(l_i (a_i - x_i), l_i (b_i - x_i)) on the
