@@ -57,6 +57,16 @@ __device__ __forceinline__ double kexp_neg(double dist) {
 #endif
 }
 
+// a stationary part's element by its run-time profile (wave-uniform), library exponential
+__device__ __forceinline__ double kprof_neg(int prof, double s2, double dist) {
+#ifdef GPR_KBUILD_NOEXP
+  return s2 * kexp_neg(dist);
+#else
+  double w;
+  return kprof_exact_w(prof, s2, dist, &w);
+#endif
+}
+
 // The 16-B-store kernels evaluate exp(-dist) by Tang's table method, ~1 ulp (kexp_s2 below;
 // the ocml exp costs ~28 instructions with its range checks and quarter-rate conversions and
 // made K-assembly VALU-bound at two SE parts).  x = -dist clamped at -800 (exp underflows to 0
@@ -91,7 +101,7 @@ __device__ __forceinline__ double sqdist(const double* xr, const double* __restr
 }
 
 // Symmetric K (same-object call): upper tiles (bi <= bj) + LDS-transposed mirror.
-template <int D>
+template <int D, bool MIX>
 __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double* __restrict__ xs,
                                                        int n, double* __restrict__ K,
                                                        size_t ldk) {
@@ -121,6 +131,7 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
       for (int k = 0; k < D; ++k) xr[k] = xrow[k];
     }
     const double s2 = kp.sig[p] * kp.sig[p];  // (any number of parts: the device table)
+    const int prof = MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int j = j0 + wv + 4 * c;  // wave-uniform column
@@ -132,7 +143,7 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
         } else {
           dist = sqdist<0>(xrow, xc, d);
         }
-        double t = s2 * kexp_neg(dist);
+        double t = MIX ? kprof_neg(prof, s2, dist) : s2 * kexp_neg(dist);
         if (i == j) t += kp.eps;
         vals[c] = (p == 0) ? t : vals[c] + t;
       }
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
 }
 
 // Cross kernel K[n x m] (x !== xp): no eps, no noise.  Rows from xs (n), cols from xps (m).
-template <int D>
+template <int D, bool MIX>
 __global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const double* __restrict__ xs,
                                                          int n, const double* __restrict__ xps,
                                                          int m, double* __restrict__ K,
@@ -188,6 +199,7 @@ __global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const doubl
       for (int k = 0; k < D; ++k) xr[k] = xrow[k];
     }
     const double s2 = kp.sig[p] * kp.sig[p];  // (any number of parts: the device table)
+    const int prof = MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int j = j0 + wv + 4 * c;
@@ -199,7 +211,7 @@ __global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const doubl
         } else {
           dist = sqdist<0>(xrow, xc, d);
         }
-        const double t = s2 * kexp_neg(dist);
+        const double t = MIX ? kprof_neg(prof, s2, dist) : s2 * kexp_neg(dist);
         vals[c] = (p == 0) ? t : vals[c] + t;
       }
     }
@@ -213,7 +225,8 @@ __global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const doubl
 
 // dK/dtheta for one hyper-parameter (src/deriv_covar.jl:20-29): part p of the composed
 // kernel, which = 0 -> (2/|sigma|) K_p (K_p incl. eps on the diagonal),
-// which = k+1 -> -2 l_k K_p (x_k,a - x_k,b)^2 with RAW x.
+// which = k+1 -> -2 l_k W_p (x_k,a - x_k,b)^2 with RAW x, W = -dk/dD of the part's profile
+// (kexp.hpp; W = K_p without eps for SquaredExp, whose branch is the expression it always was).
 __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
                              const double* __restrict__ xs, int n, int p, int which,
                              double* __restrict__ DK, size_t ld) {
@@ -228,7 +241,8 @@ __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
       const double q = xa[k] - xb[k];
       s = fma(q, q, s);
     }
-    double Kp = kp.sig[p] * kp.sig[p] * exp(-1.0 * s);
+    double W;
+    double Kp = kprof_exact_w((int)kp.pf[p], kp.sig[p] * kp.sig[p], s, &W);
     if (a == b) Kp += kp.eps;
     double v;
     if (which == 0) {
@@ -236,7 +250,7 @@ __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
     } else {
       const int k = which - 1;
       const double dx = X[(size_t)a * d + k] - X[(size_t)b * d + k];
-      v = -2.0 * kp.l[(size_t)p * d + k] * Kp * (dx * dx);
+      v = -2.0 * kp.l[(size_t)p * d + k] * W * (dx * dx);
     }
     DK[(size_t)a + (size_t)b * ld] = v;
   }
@@ -304,7 +318,9 @@ constexpr int KT_LDS = KT * (KT + 1);  // doubles; also holds the 64 x D column 
 // One 64 x 64 tile of K (or cross K), all SE parts summed in part order (src/compose_covar.jl:
 // 52-56).  DIAG: a diagonal tile of the symmetric K -- eps per SE part and sigma_n^2 on i == j
 // (only these 1/nt of the tiles pay the index compares).  tabs = nse tables of 256 doubles.
-template <int D, bool DIAG>
+// MIX: some part is a Matern part -- each part's element loop is entered through one scalar
+// branch on its profile (kprof_dispatch); MIX = false compiles the SquaredExp loop alone.
+template <int D, bool DIAG, bool MIX>
 __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const double* __restrict__ xs,
                                                   int n, const double* __restrict__ xcs, int m,
                                                   int i0, int j0, double* lds, const double* tabs,
@@ -338,6 +354,7 @@ __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const doubl
     const double* ts = tabs + 256 * p;
     // columns in groups of KB_CG: KB_CG x 2 independent distance accumulators, k outermost
     // (smaller groups keep fewer exp evaluations in flight: register pressure / occupancy)
+    kprof_dispatch<MIX>(MIX ? kp.prof[p] : 0, [&](auto pf) {
 #pragma unroll
     for (int cb = 0; cb < 8; cb += KB_CG) {
       double d0[KB_CG], d1[KB_CG];
@@ -355,7 +372,8 @@ __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const doubl
       }
 #pragma unroll
       for (int c = 0; c < KB_CG; ++c) {
-        double t0 = kexp_s2(d0[c], ts), t1 = kexp_s2(d1[c], ts);
+        constexpr int PF = decltype(pf)::value;
+        double t0 = kprof_s2<PF>(d0[c], ts), t1 = kprof_s2<PF>(d1[c], ts);
         if (DIAG) {
           const int j = j0 + cg + 8 * (cb + c), i = i0 + 2 * l32;
           if (i == j) t0 += kp.eps;
@@ -365,6 +383,7 @@ __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const doubl
         v[cb + c][1] += t1;
       }
     }
+    });
   }
   if (DIAG && kp.has_noise) {
 #pragma unroll
@@ -406,7 +425,7 @@ __device__ __forceinline__ void store_pair(double* K, size_t idx, bool ok0, bool
   }
 }
 
-template <int D>
+template <int D, bool MIX>
 __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams kp, const double* __restrict__ xs,
                                                         int n, double* __restrict__ K, size_t ldk,
                                                         int ntiles) {
@@ -426,9 +445,9 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams
     const int i0 = bi * KT, j0 = bj * KT;
     double v[8][2];
     if (bi == bj)
-      kmat_tile_compute<D, true>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
+      kmat_tile_compute<D, true, MIX>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
     else
-      kmat_tile_compute<D, false>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
+      kmat_tile_compute<D, false, MIX>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
     const int i = i0 + 2 * l32;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -456,7 +475,7 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams
   }
 }
 
-template <int D>
+template <int D, bool MIX>
 __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_cross2_kernel(KParams kp, const double* __restrict__ xs,
                                                           int n, const double* __restrict__ xps,
                                                           int m, double* __restrict__ K,
@@ -471,7 +490,7 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_cross2_kernel(KPara
     const int bi = bid % ntile_i, bj = bid / ntile_i;
     const int i0 = bi * KT, j0 = bj * KT;
     double v[8][2];
-    kmat_tile_compute<D, false>(kp, xs, n, xps, m, i0, j0, lds, tabs, v);
+    kmat_tile_compute<D, false, MIX>(kp, xs, n, xps, m, i0, j0, lds, tabs, v);
     const int i = i0 + 2 * l32;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -489,11 +508,17 @@ void launch_sym(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, double
     if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {  // (their LDS tables hold KMAXP parts)
       const int grid = (int)std::min<long long>(nblk, kbuild_grid());
       const size_t lds_bytes = sizeof(double) * (KT_LDS + 256 * kp.nse);
-      kmat_sym2_kernel<D><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
+      if (kp.mix)
+        kmat_sym2_kernel<D, true><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
+      else
+        kmat_sym2_kernel<D, false><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
       return;
     }
   }
-  kmat_sym_kernel<D><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, K, (size_t)ldk);
+  if (kp.mix)
+    kmat_sym_kernel<D, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, K, (size_t)ldk);
+  else
+    kmat_sym_kernel<D, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, K, (size_t)ldk);
 }
 
 template <int D>
@@ -505,12 +530,19 @@ void launch_cross(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, cons
     if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {  // (their LDS tables hold KMAXP parts)
       const int grid = (int)std::min<long long>(nblk, kbuild_grid());
       const size_t lds_bytes = sizeof(double) * (KT * D + 256 * kp.nse);
-      kmat_cross2_kernel<D><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk,
-                                                                   nti, (int)nblk);
+      if (kp.mix)
+        kmat_cross2_kernel<D, true><<<grid, 256, lds_bytes, ctx->stream>>>(
+            kp, xs, n, xps, m, K, (size_t)ldk, nti, (int)nblk);
+      else
+        kmat_cross2_kernel<D, false><<<grid, 256, lds_bytes, ctx->stream>>>(
+            kp, xs, n, xps, m, K, (size_t)ldk, nti, (int)nblk);
       return;
     }
   }
-  kmat_cross_kernel<D><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
+  if (kp.mix)
+    kmat_cross_kernel<D, true><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
+  else
+    kmat_cross_kernel<D, false><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
 }
 
 // ---- Gram form of the distance on FP64 MFMA ---------------------------------------------
@@ -585,7 +617,7 @@ __global__ void gram_prep_kernel(const double* __restrict__ xs, int n, int d, in
 // One 64 x 64 tile of K on MFMA + VALU, SE parts summed in order.  Wave w owns the 32 x 32
 // quadrant (rows 32 (w & 1), cols 32 (w >> 1)): 2 x 2 blocks of 16 x 16; lane l / register q of
 // block (rb, cb) <-> row 16 rb + (l >> 4) + 4 q, col 16 cb + (l & 15).
-template <int S, bool DIAG>
+template <int S, bool DIAG, bool MIX>
 __device__ __forceinline__ void gram_tile(const KParams& kp, const double* __restrict__ gA,
                                           const double* __restrict__ gB, const double* __restrict__ nA,
                                           const double* __restrict__ nB, int nblkA, int nblkB,
@@ -626,6 +658,7 @@ __device__ __forceinline__ void gram_tile(const KParams& kp, const double* __res
           acc[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][s], b[cb][s], acc[rb][cb], 0, 0, 0);
       }
     const double* ts = tabs + 256 * p;
+    kprof_dispatch<MIX>(MIX ? kp.prof[p] : 0, [&](auto pf) {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -638,11 +671,12 @@ __device__ __forceinline__ void gram_tile(const KParams& kp, const double* __res
             on_diag = wr == wc && rb == cb && (lane >> 4) + 4 * q == (lane & 15);
             if (on_diag) x = 0.0;
           }
-          double t = kexp_s2(-x, ts);
+          double t = kprof_s2<decltype(pf)::value>(-x, ts);
           if (DIAG && on_diag) t += kp.eps;
           v[rb][cb][q] += t;
           if ((q + 1) % GRAM_EXPG == 0) __builtin_amdgcn_sched_barrier(0);
         }
+    });
   }
   if (DIAG && kp.has_noise && wr == wc) {
 #pragma unroll
@@ -675,8 +709,8 @@ __device__ __forceinline__ void tri_tile(int bid, int* bi, int* bj) {
   *bi = __builtin_amdgcn_readfirstlane(bid - j * (j + 1) / 2);
 }
 
-template <int S>
-__global__ __launch_bounds__(256, 4) void kmat_symg_kernel(KParams kp, const double* __restrict__ gA,
+template <int S, bool MIX>
+__global__ __launch_bounds__(256, MIX ? 3 : 4) void kmat_symg_kernel(KParams kp, const double* __restrict__ gA,
                                                          const double* __restrict__ gB,
                                                          const double* __restrict__ nrm, int nblk,
                                                          int n, double* __restrict__ K, size_t ldk,
@@ -693,9 +727,9 @@ __global__ __launch_bounds__(256, 4) void kmat_symg_kernel(KParams kp, const dou
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
     if (bi == bj)
-      gram_tile<S, true>(kp, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile<S, true, MIX>(kp, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
     else
-      gram_tile<S, false>(kp, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile<S, false, MIX>(kp, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
     __syncthreads();  // previous tile's LDS reads are done
     gram_to_lds(v, T);
     __syncthreads();
@@ -731,8 +765,8 @@ __global__ __launch_bounds__(256, 4) void kmat_symg_kernel(KParams kp, const dou
   }
 }
 
-template <int S>
-__global__ __launch_bounds__(256, 4) void kmat_crossg_kernel(KParams kp, const double* __restrict__ gA,
+template <int S, bool MIX>
+__global__ __launch_bounds__(256, MIX ? 3 : 4) void kmat_crossg_kernel(KParams kp, const double* __restrict__ gA,
                                                            const double* __restrict__ gB,
                                                            const double* __restrict__ nrmA,
                                                            const double* __restrict__ nrmB,
@@ -750,7 +784,7 @@ __global__ __launch_bounds__(256, 4) void kmat_crossg_kernel(KParams kp, const d
     const int bj = __builtin_amdgcn_readfirstlane(bid / ntile_i);
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
-    gram_tile<S, false>(kp, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
+    gram_tile<S, false, MIX>(kp, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
     __syncthreads();
     gram_to_lds(v, T);
     __syncthreads();
@@ -781,7 +815,7 @@ __global__ __launch_bounds__(256, 4) void kmat_crossg_kernel(KParams kp, const d
 // order, so the element sum stays ((p1 + p2) + p3) + ... across launches.
 constexpr int GR_CH = 4;  // k-steps per chunk
 
-template <bool DIAG>
+template <bool DIAG, bool MIX>
 __device__ __forceinline__ void gram_tile_rt(const KParams& kp, int S, const double* __restrict__ gA,
                                              const double* __restrict__ gB,
                                              const double* __restrict__ nA,
@@ -846,6 +880,7 @@ __device__ __forceinline__ void gram_tile_rt(const KParams& kp, int S, const dou
       }
     }
     const double* ts = tabs + 256 * p;
+    kprof_dispatch<MIX>(MIX ? kp.prof[p] : 0, [&](auto pf) {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -858,11 +893,12 @@ __device__ __forceinline__ void gram_tile_rt(const KParams& kp, int S, const dou
             on_diag = wr == wc && rb == cb && (lane >> 4) + 4 * q == (lane & 15);
             if (on_diag) x = 0.0;
           }
-          double t = kexp_s2(-x, ts);
+          double t = kprof_s2<decltype(pf)::value>(-x, ts);
           if (DIAG && on_diag) t += kp.eps;
           v[rb][cb][q] += t;
           if ((q + 1) % GRAM_EXPG == 0) __builtin_amdgcn_sched_barrier(0);
         }
+    });
   }
   if (DIAG && kp.has_noise && wr == wc) {
 #pragma unroll
@@ -916,7 +952,7 @@ __device__ __forceinline__ void gram_tile_init(const double* __restrict__ K, siz
       for (int q = 0; q < 4; ++q) v[rb][cb][q] = T[(c0 + 16 * cb) * (KT + 1) + r0 + 16 * rb + 4 * q];
 }
 
-template <bool ACC>
+template <bool ACC, bool MIX>
 __global__ __launch_bounds__(256, 2) void kmat_symgr_kernel(KParams kp, int S,
                                                             const double* __restrict__ gA,
                                                             const double* __restrict__ gB,
@@ -936,9 +972,9 @@ __global__ __launch_bounds__(256, 2) void kmat_symgr_kernel(KParams kp, int S,
     gd4 v[2][2];
     gram_tile_init<ACC>(K, ldk, i0, j0, n, n, T, v);
     if (bi == bj)
-      gram_tile_rt<true>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile_rt<true, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
     else
-      gram_tile_rt<false>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile_rt<false, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
     __syncthreads();  // previous tile's LDS reads are done
     gram_to_lds(v, T);
     __syncthreads();
@@ -972,7 +1008,7 @@ __global__ __launch_bounds__(256, 2) void kmat_symgr_kernel(KParams kp, int S,
   }
 }
 
-template <bool ACC>
+template <bool ACC, bool MIX>
 __global__ __launch_bounds__(256, 2) void kmat_crossgr_kernel(
     KParams kp, int S, const double* __restrict__ gA, const double* __restrict__ gB,
     const double* __restrict__ nrmA, const double* __restrict__ nrmB, int nblkA, int nblkB, int n,
@@ -989,7 +1025,7 @@ __global__ __launch_bounds__(256, 2) void kmat_crossgr_kernel(
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
     gram_tile_init<ACC>(K, ldk, i0, j0, n, m, T, v);
-    gram_tile_rt<false>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
+    gram_tile_rt<false, MIX>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
     __syncthreads();
     gram_to_lds(v, T);
     __syncthreads();
@@ -1289,9 +1325,9 @@ inline size_t gram_centres_cap(const KParams& kp) {
 
 // S > 0: the kernels compiled for S k-steps; S = 0: the run-time-S kernels (any d), which with
 // acc add their parts to the K already stored (launch_gram_groups)
-template <int SC>
-int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
-                int m, int same, double* K, int ldk, int acc = 0) {
+template <int SC, bool MIX>
+int launch_gram_m(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
+                  int m, int same, double* K, int ldk, int acc) {
   const int d = kp.d;
   const int S = SC > 0 ? SC : (d + 3) / 4;
   const int nbA = ((n + KT - 1) / KT) * (KT / 16);
@@ -1322,33 +1358,43 @@ int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const 
     const long long nblk = (long long)nt * (nt + 1) / 2;
     const int grid = (int)std::min<long long>(nblk, kbuild_grid());
     if constexpr (SC > 0)
-      kmat_symg_kernel<SC><<<grid, 256, lds_bytes, ctx->stream>>>(kp, A, B, nrmA, nbA, n, K,
+      kmat_symg_kernel<SC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, A, B, nrmA, nbA, n, K,
                                                                   (size_t)ldk, (int)nblk);
     else if (acc)
-      kmat_symgr_kernel<true><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
+      kmat_symgr_kernel<true, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
                                                                      (size_t)ldk, (int)nblk);
     else
-      kmat_symgr_kernel<false><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
+      kmat_symgr_kernel<false, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
                                                                       (size_t)ldk, (int)nblk);
   } else {
     const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
     const long long nblk = (long long)nti * ntj;
     const int grid = (int)std::min<long long>(nblk, kbuild_grid());
     if constexpr (SC > 0)
-      kmat_crossg_kernel<SC><<<grid, 256, lds_bytes, ctx->stream>>>(
+      kmat_crossg_kernel<SC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
           kp, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
     else if (acc)
-      kmat_crossgr_kernel<true><<<grid, 256, lds_bytes, ctx->stream>>>(
+      kmat_crossgr_kernel<true, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
           kp, S, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
     else
-      kmat_crossgr_kernel<false><<<grid, 256, lds_bytes, ctx->stream>>>(
+      kmat_crossgr_kernel<false, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
           kp, S, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
   }
   LAUNCH_CHECK(ctx);
   return 0;
 }
 
-// the upper-only build (kmat_symu_kernel): operands as launch_gram's same-object path
+// SE-only descriptions (and SE-only groups of a mixed one) launch the instantiations they
+// always launched; a group with a Matern part the MIX ones (one scalar branch per part)
+template <int SC>
+int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
+                int m, int same, double* K, int ldk, int acc = 0) {
+  return kp.mix ? launch_gram_m<SC, true>(ctx, kp, xs, n, xps, m, same, K, ldk, acc)
+                : launch_gram_m<SC, false>(ctx, kp, xs, n, xps, m, same, K, ldk, acc);
+}
+
+// the upper-only build (kmat_symu_kernel, SquaredExp parts only): operands as launch_gram's
+// same-object path
 template <int S, int NSE>
 int launch_gram_upper(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, double* K, int ldk,
                       int full) {
@@ -1543,7 +1589,9 @@ int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kp, const double* dX, int 
     // one SE part: both halves computed by the column build (store-bound: one exponential per
     // element is cheaper than the mirrored tiles' store pattern); more parts: upper tiles
     // computed once and mirrored through LDS (the exponentials dominate)
-    if (gram_enabled(ctx, kp.d) && kp.d <= GRAM_CT_MAXD && kp.nse <= 1)
+    // (SquaredExp only: a description with a Matern part takes the mirrored tiles)
+    if (gram_enabled(ctx, kp.d) && kp.d <= GRAM_CT_MAXD && kp.nse <= 1 && !kp.mix &&
+        !(ctx->kbuild_tiles && vec_store_ok(dK, ldk)))
       return kp.nse == 1 ? launch_gram_upper_s<1>(ctx, kp, ctx->dxs, n, dK, ldk, 1)
                          : launch_gram_upper_s<2>(ctx, kp, ctx->dxs, n, dK, ldk, 1);
     if (gram_enabled(ctx, kp.d) && vec_store_ok(dK, ldk))
@@ -1567,9 +1615,10 @@ int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kp, const doubl
                                     double* dK, int ldk) {
   ctx->kup_ptr = nullptr;
   // upper-only where the tile-DAG will take exactly this matrix directly (potrf_core), with
-  // the Gram form (d <= 20) and one or two SE parts; the full symmetric K otherwise
+  // the Gram form (d <= 20) and one or two SquaredExp parts; the full symmetric K otherwise
+  // (any description with a Matern part: kmat_symu_kernel is not specialised for them)
   const bool upper = ctx->kbuild_upper && n > 0 && gram_enabled(ctx, kp.d) &&
-                     kp.d <= GRAM_CT_MAXD && kp.nse <= 2 &&
+                     kp.d <= GRAM_CT_MAXD && kp.nse <= 2 && !kp.mix &&
                      dag_takes_whole(ctx, n, ldk, dK) && dag_shape_ok(n, ldk, dK);
   if (!upper) return launch_kernel_matrix(ctx, kp, dX, n, nullptr, n, 1, dK, ldk);
   GPR_TRY(scale_inputs(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));
@@ -1634,7 +1683,7 @@ int gpr_kernel(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
   if (n < 0) return set_err(ctx, GPR_E_ARG, "n < 0");
   if (same != GPR_CROSS && same != GPR_SELF && same != GPR_SAME_OBJECT)
     return set_err(ctx, GPR_E_ARG, "same=%d is not GPR_CROSS, GPR_SELF or GPR_SAME_OBJECT", same);
-  if (same == GPR_SAME_OBJECT) kp.has_noise = 0;  // 5-arg x === xp: eps per SE part, no noise
+  if (same == GPR_SAME_OBJECT) kp.has_noise = 0;  // 5-arg x === xp: eps per stationary part, no noise
   if (same) m = n;
   else if (!dXp) return set_err(ctx, GPR_E_ARG, "dXp is NULL for a cross kernel");
   if (ldk < (n > 1 ? n : 1)) return set_err(ctx, GPR_E_ARG, "ldk=%d < n=%d", ldk, n);
@@ -1651,7 +1700,7 @@ int gpr_kernel_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
   // find_idx (src/compose_covar.jl:109-115)
   int off = 0, se = 0;
   for (int t = 0; t < nk; ++t) {
-    const int w = kinds[t] == GPR_SE ? d + 1 : 1;
+    const int w = kinds[t] != GPR_WN ? d + 1 : 1;
     if (i - 1 < off + w) {
       const int local = i - 1 - off;
       const int blocks = (int)std::min<long long>(((long long)n * n + 255) / 256, 8192);
@@ -1668,7 +1717,7 @@ int gpr_kernel_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
       return 0;
     }
     off += w;
-    if (kinds[t] == GPR_SE) ++se;
+    if (kinds[t] != GPR_WN) ++se;
   }
   return set_err(ctx, GPR_E_ARG, "hp index not found");
 }

@@ -8,64 +8,108 @@
 
 #include "../../include/gpr_hip.h"
 
-#define KMAXP 4   // SquaredExp parts one fused-kernel launch handles (more: groups of KMAXP)
+#define KMAXP 4   // stationary parts one fused-kernel launch handles (more: groups of KMAXP)
+
+// Radial profile of a stationary part: k = sigma^2 f(D) of the ARD-scaled squared distance D
+// (kexp.hpp).  SE is the reference's; the two Matern profiles are this library's own.
+enum { KPROF_SE = 0, KPROF_M32 = 1, KPROF_M52 = 2 };
+inline bool kind_stationary(int kind) {
+  return kind == GPR_SE || kind == GPR_M32 || kind == GPR_M52;
+}
+inline int kind_profile(int kind) {
+  return kind == GPR_M32 ? KPROF_M32 : kind == GPR_M52 ? KPROF_M52 : KPROF_SE;
+}
+inline const char* kind_name(int kind) {
+  return kind == GPR_SE ? "SquaredExp" : kind == GPR_M32 ? "Matern32" : kind == GPR_M52 ? "Matern52"
+         : kind == GPR_WN ? "WhiteNoise" : "?";
+}
 
 // Kernel description passed BY VALUE to every assembly kernel (a few dozen bytes of kernargs;
 // the per-part tables live in the context's parameter block, see KParBlock).
-// Mirrors split(hp, dims) of src/compose_covar.jl:21-28: the SE parts in `+` order
+// Mirrors split(hp, dims) of src/compose_covar.jl:21-28: the stationary parts (SquaredExp,
+// Matern32, Matern52: hp [sigma, l_1..l_d] each) in `+` order
 // and the first WhiteNoise part (add_noise! src/compose_covar.jl:63-71).  Any d >= 1 and any
 // number of parts, as the reference.
 struct KParams {
   int d;          // input dimension
-  int nse;        // number of SquaredExp parts (>= 1)
+  int nse;        // number of stationary parts (>= 1)
   int has_noise;  // a WhiteNoise part is present
-  double eps;                    // jitter per SE part on a same-object diagonal
+  double eps;                    // jitter per stationary part on a same-object diagonal
   double noise2;                 // sigma_n^2
   double noise_sigma;            // sigma_n
-  double sigma[KMAXP];           // sigma of the first KMAXP SE parts -- of the launch's group of
+  double sigma[KMAXP];           // sigma of the first KMAXP parts -- of the launch's group of
                                  // parts where a launcher narrows the description (kparams_group)
   // device tables of ALL parts in this call's slot of the context's parameter block, filled in
   // stream order by make_kparams: valid for launches on the context's streams until
   // KParBlock::NSLOT further descriptions have been made on the context
   const double* l;               // [nse][d] inverse length-scales (multipliers)
   const double* l2;              // [nse][d] their squares (the gradient pass's distance)
-  const double* sig;             // [nse]    sigma of every SE part
+  const double* sig;             // [nse]    sigma of every stationary part
+  const double* pf;              // [nse]    profile code (KPROF_*, as a double) of every part
   const double* exptab;          // device table 2^(j/256), j < 256 (ctx->dexptab)
   // the caller's description (host; valid during the C call): sigma of any part via kp_sigma
   const int* kinds;
   int nk;
   const double* hp;
+  // profiles, by value (wave-uniform kernel arguments): prof[] follows sigma[] (the first KMAXP
+  // parts, or the launch's group); mix = some part of this description (of the group, where
+  // narrowed) is not SquaredExp -- selects the kernels' MIX instantiations, SE-only
+  // descriptions launch the SE instantiations
+  int prof[KMAXP];
+  int mix;
 };
 
-// sigma of SE part p (host side, any p < nse)
-inline double kp_sigma(const KParams& kp, int p) {
+// sigma / profile of stationary part p (host side, any p < nse)
+inline double kp_sigma(const KParams& kp, int p, int* prof = nullptr) {
   int off = 0, se = 0;
   for (int i = 0; i < kp.nk; ++i) {
-    if (kp.kinds[i] == GPR_SE) {
-      if (se++ == p) return kp.hp[off];
+    if (kp.kinds[i] != GPR_WN) {
+      if (se++ == p) {
+        if (prof) *prof = kind_profile(kp.kinds[i]);
+        return kp.hp[off];
+      }
       off += kp.d + 1;
     } else {
       off += 1;
     }
   }
+  if (prof) *prof = KPROF_SE;
   return 0.0;
 }
+// the first part that is not SquaredExp / WhiteNoise (its kind), or 0: the calls that rely on
+// SE's separability or its closed-form integrals refuse such a description (GPR_E_UNSUP)
+inline int kinds_first_matern(const int* kinds, int nk, int* index) {
+  for (int i = 0; i < nk; ++i)
+    if (kinds[i] == GPR_M32 || kinds[i] == GPR_M52) {
+      if (index) *index = i;
+      return kinds[i];
+    }
+  return 0;
+}
 
-// The description narrowed to SE parts [p0, p0 + cnt) (cnt <= KMAXP) for one launch of the
-// fused kernels: sigma[] and the device tables start at part p0; has_noise as given.
+// The description narrowed to stationary parts [p0, p0 + cnt) (cnt <= KMAXP) for one launch of
+// the fused kernels: sigma[], prof[] and the device tables start at part p0 (a profile follows
+// its part); mix is the group's own; has_noise as given.
 inline KParams kparams_group(const KParams& kp, int p0, int cnt, int has_noise) {
   KParams g = kp;
   g.nse = cnt;
   g.has_noise = has_noise;
-  for (int p = 0; p < KMAXP; ++p) g.sigma[p] = p < cnt ? kp_sigma(kp, p0 + p) : 0.0;
+  g.mix = 0;
+  for (int p = 0; p < KMAXP; ++p) {
+    g.prof[p] = KPROF_SE;
+    g.sigma[p] = p < cnt ? kp_sigma(kp, p0 + p, &g.prof[p]) : 0.0;
+    if (g.prof[p] != KPROF_SE) g.mix = 1;
+  }
   g.l = kp.l + (size_t)p0 * kp.d;
   g.l2 = kp.l2 + (size_t)p0 * kp.d;
   g.sig = kp.sig + p0;
+  g.pf = kp.pf + p0;
   return g;
 }
 
-// Per-context parameter block: NSLOT device slots of `cap` doubles ([l | l2 | sigma] of one
-// kernel description each) and as many pinned host staging slots.  make_kparams fills host
+// Per-context parameter block: NSLOT device slots of `cap` doubles ([l | l2 | sigma | profile]
+// of one kernel description each; the profile codes are part of the block, so that the
+// comparison with the description made last tells SquaredExp from Matern at equal hp) and as many pinned host staging slots.  make_kparams fills host
 // slot `next`, uploads it in stream order and records ev[next] -- unless the tables equal those
 // of the description made last, whose slot then serves again; a slot is re-filled only once
 // its previous upload has completed (NSLOT descriptions later: the wait does not block in
@@ -241,6 +285,8 @@ struct gpr_ctx {
   int kbuild_gram_maxd = 1 << 30;  // GPR_KBUILD_GRAM_MAXD: largest d that takes the Gram form
                                 // (20: the compile-time-S kernels only, difference form above)
   KParBlock kpar;               // kernel-description tables (make_kparams)
+  int kbuild_tiles = 0;         // GPR_KBUILD_TILES=1: one SE part's symmetric K by the mirrored
+                                // tiles too (A/B runs against the Matern profiles)
   int kbuild_colstore = 1;      // GPR_KBUILD_COLSTORE=0: single-part upper builds store in the
                                 // MFMA D layout instead of 1-KB column segments
   int cv_batch = 1;             // GPR_CV_BATCH=0: cv_batch folds one by one on child contexts
@@ -283,6 +329,16 @@ void copy_knobs(const gpr_ctx* from, gpr_ctx* to);
   } while (0)
 
 #define LAUNCH_CHECK(ctx) HIP_TRY(ctx, hipGetLastError())
+
+// the calls built on SquaredExp's separability or its closed-form integrals: GPR_E_UNSUP,
+// naming the part, before anything is computed or written
+inline int refuse_matern(gpr_ctx* ctx, const int* kinds, int nk, const char* what) {
+  int idx = 0;
+  const int kind = kinds ? kinds_first_matern(kinds, nk, &idx) : 0;
+  if (!kind) return 0;
+  return set_err(ctx, GPR_E_UNSUP, "%s needs SquaredExp parts: part %d is %s", what, idx + 1,
+                 kind_name(kind));
+}
 
 // ---- workspace ------------------------------------------------------------------------
 int ensure_buf(gpr_ctx* ctx, double** p, size_t* cap, size_t need_doubles);

@@ -93,17 +93,20 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   memset(kp, 0, sizeof *kp);
   int nse = 0;
   for (int i = 0; i < nk; ++i) {
-    if (kinds[i] == GPR_SE) ++nse;
+    if (kind_stationary(kinds[i])) ++nse;
     else if (kinds[i] != GPR_WN) return set_err(ctx, GPR_E_ARG, "unknown kernel kind %d", kinds[i]);
   }
-  if (nse == 0) return set_err(ctx, GPR_E_ARG, "kernel needs at least one SquaredExp part");
-  // this description's slot of the parameter block: [l (nse d) | l2 (nse d) | sigma (nse)]
+  if (nse == 0)
+    return set_err(ctx, GPR_E_ARG, "kernel needs at least one stationary part (SquaredExp, "
+                                   "Matern32 or Matern52)");
+  // this description's slot of the parameter block:
+  // [l (nse d) | l2 (nse d) | sigma (nse) | profile (nse)]
   KParBlock& kb = ctx->kpar;
-  const size_t nl = (size_t)nse * d, need = 2 * nl + nse;
+  const size_t nl = (size_t)nse * d, need = 2 * nl + 2 * (size_t)nse;
   if (need > kb.cap || !kb.dev) {
     // (first use, or a description past every earlier one: never inside the 4 x 64 envelope
     // once the block exists)
-    const size_t cap = std::max(need, (size_t)(2 * 4 * 64 + 4));
+    const size_t cap = std::max(need, (size_t)(2 * 4 * 64 + 2 * 4));
     if (kb.dev) {
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       HIP_TRY(ctx, hipFree(kb.dev));
@@ -134,9 +137,15 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   kp->hp = hp;
   int off = 0;
   for (int i = 0; i < nk; ++i) {
-    if (kinds[i] == GPR_SE) {
-      if (kp->nse < KMAXP) kp->sigma[kp->nse] = hp[off];
+    if (kinds[i] != GPR_WN) {
+      const int prof = kind_profile(kinds[i]);
+      if (kp->nse < KMAXP) {
+        kp->sigma[kp->nse] = hp[off];
+        kp->prof[kp->nse] = prof;
+      }
+      if (prof != KPROF_SE) kp->mix = 1;
       hl[2 * nl + kp->nse] = hp[off];
+      hl[2 * nl + nse + kp->nse] = (double)prof;
       for (int k = 0; k < d; ++k) {
         hl[(size_t)kp->nse * d + k] = hp[off + 1 + k];
         hl[nl + (size_t)kp->nse * d + k] = hp[off + 1 + k] * hp[off + 1 + k];
@@ -173,6 +182,7 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   kp->l = dl;
   kp->l2 = dl + nl;
   kp->sig = dl + 2 * nl;
+  kp->pf = dl + 2 * nl + nse;
   if (D_total) *D_total = off;
   return 0;
 }
@@ -201,6 +211,7 @@ const Knob kKnobs[] = {
     {"GPR_KBUILD_UPPER", &gpr_ctx::kbuild_upper, nullptr},
     {"GPR_KBUILD_EXACT", &gpr_ctx::kbuild_exact, nullptr},
     {"GPR_KBUILD_COLSTORE", &gpr_ctx::kbuild_colstore, nullptr},
+    {"GPR_KBUILD_TILES", &gpr_ctx::kbuild_tiles, nullptr},
     {"GPR_KBUILD_GRAM_MAXD", &gpr_ctx::kbuild_gram_maxd, nullptr},
     {"GPR_CV_STREAMS", &gpr_ctx::cv_streams, nullptr},
     {"GPR_CV_BATCH", &gpr_ctx::cv_batch, nullptr},

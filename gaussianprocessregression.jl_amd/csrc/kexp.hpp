@@ -54,6 +54,94 @@ static __device__ __forceinline__ double kexp_s2(double dist, const double* ts) 
 #endif
 }
 
+// ---- radial profiles of the stationary parts -----------------------------------------------
+// k = sigma^2 f(D) of the ARD-scaled squared distance D = sum_k (l_k (x_k - x'_k))^2, and
+// W = -dk/dD (what the length-scale derivatives need: dk/dl_k = -2 l_k W (x_k - x'_k)^2):
+//   PF = 0  SquaredExp  k = s2 exp(-D)                           W = k
+//   PF = 1  Matern-3/2  k = s2 (1 + a r) exp(-a r),     a = 3^.5  W = s2 (3/2) exp(-a r)
+//   PF = 2  Matern-5/2  k = s2 (1 + a r + (a r)^2 / 3) exp(-a r), a = 5^.5
+//                                                                W = s2 (5/6) (1 + a r) exp(-a r)
+// with r = sqrt(max(D, 0)) (the codes are KPROF_* of common.hpp).  The clamp matters: the Gram
+// form of the distance returns D a few 1e-16 BELOW zero for coincident points, which exp never
+// noticed and a square root turns into NaN.  (A NaN D fails the compare and propagates.)  The
+// exponential is the table one above with s2 folded in, so a Matern element costs the SE
+// element plus one FP64 square root and two or three FMAs.  The profile is per part, i.e.
+// wave-uniform: callers branch on it once per part (kprof_dispatch), outside their element
+// loops, and the element code is compiled per profile.
+template <int PF>
+static __device__ __forceinline__ double kprof_s2(double D, const double* ts) {
+  if constexpr (PF == 0) {
+    return kexp_s2(D, ts);
+  } else {
+    const double ar = (PF == 1 ? 1.7320508075688772 : 2.23606797749979) *
+                      __builtin_sqrt(D < 0.0 ? 0.0 : D);
+    const double e = kexp_s2(ar, ts);
+    double poly = 1.0 + ar;
+    if constexpr (PF == 2) poly = fma(ar * ar, 1.0 / 3.0, poly);
+    return e * poly;
+  }
+}
+
+// the same, also returning W = -dk/dD (finite at r = 0)
+template <int PF>
+static __device__ __forceinline__ double kprof_s2_w(double D, const double* ts, double* W) {
+  if constexpr (PF == 0) {
+    const double k = kexp_s2(D, ts);
+    *W = k;
+    return k;
+  } else {
+    const double ar = (PF == 1 ? 1.7320508075688772 : 2.23606797749979) *
+                      __builtin_sqrt(D < 0.0 ? 0.0 : D);
+    const double e = kexp_s2(ar, ts);
+    double poly = 1.0 + ar;
+    if constexpr (PF == 1) {
+      *W = 1.5 * e;
+    } else {
+      *W = (5.0 / 6.0) * (e * poly);
+      poly = fma(ar * ar, 1.0 / 3.0, poly);
+    }
+    return e * poly;
+  }
+}
+
+// the profiles with the library exponential (the difference-form fallback kernels, dK/dtheta):
+// prof is a run-time, wave-uniform code
+static __device__ __forceinline__ double kprof_exact_w(int prof, double s2, double D, double* W) {
+  if (prof == 0) {
+    const double k = s2 * exp(-1.0 * D);
+    *W = k;
+    return k;
+  }
+  const double ar = (prof == 1 ? 1.7320508075688772 : 2.23606797749979) *
+                    __builtin_sqrt(D < 0.0 ? 0.0 : D);
+  const double e = s2 * exp(-1.0 * ar);
+  double poly = 1.0 + ar;
+  if (prof == 1) {
+    *W = 1.5 * e;
+  } else {
+    *W = (5.0 / 6.0) * (e * poly);
+    poly = fma(ar * ar, 1.0 / 3.0, poly);
+  }
+  return e * poly;
+}
+
+// f(tag) with tag = kprof_tag<profile>: one scalar branch per call.  MIX =
+// false compiles the SquaredExp body alone (the instantiations SE-only descriptions launch).
+template <int PF>
+struct kprof_tag {
+  static constexpr int value = PF;
+};
+template <bool MIX, class F>
+static __device__ __forceinline__ void kprof_dispatch(int prof, F&& f) {
+  if constexpr (!MIX) {
+    f(kprof_tag<0>{});
+  } else {
+    if (prof == 1) f(kprof_tag<1>{});
+    else if (prof == 2) f(kprof_tag<2>{});
+    else f(kprof_tag<0>{});
+  }
+}
+
 // the same without the clamp (3 VALU fewer), for callers that have bounded dist < 5.8e6, so
 // that n fits the int32 low word: below -745 the ldexp underflows to 0 as in the clamped form,
 // and a NaN propagates

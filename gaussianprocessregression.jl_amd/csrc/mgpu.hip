@@ -538,6 +538,13 @@ int gpr_split_predict_mgpu(gpr_mgpu_t h, const int* kinds, int nk, const double*
     return mg_err(h, GPR_E_ARG, "bad args");
   if (fit_mode != GPR_MGPU_BROADCAST && fit_mode != GPR_MGPU_REPLICATE)
     return mg_err(h, GPR_E_ARG, "fit_mode %d is neither GPR_MGPU_BROADCAST nor _REPLICATE", fit_mode);
+  {  // (before any device starts: the split prediction is built on SquaredExp's separability)
+    int idx = 0;
+    const int kind = kinds_first_matern(kinds, nk, &idx);
+    if (kind)
+      return mg_err(h, GPR_E_UNSUP, "split prediction needs SquaredExp parts: part %d is %s",
+                    idx + 1, kind_name(kind));
+  }
   const int G = h->ngpu;
   // GPR_MGPU_SELF_BCAST=1 (tests on a one-GPU box): the broadcast path even for one device,
   // which then also acts as a receiver (pack, 1-rank RCCL broadcast, unpack, forget)

@@ -8,7 +8,8 @@
 // Here all D components come out of ONE pass over the upper triangle of K^{-1}:
 //   g_i = -0.5 sum_ab M_ab dK_i,ab,   M = alpha alpha^T - K^{-1}
 // with dK recomputed in registers from x:  dK/dsigma = (2/|sigma|) K_p (incl. eps on the
-// diagonal), dK/dl_k = -2 l_k K_p (x_k,a - x_k,b)^2 (raw x), dK/dsigma_n = 2 sigma_n I.
+// diagonal), dK/dl_k = -2 l_k W_p (x_k,a - x_k,b)^2 (raw x; W = -dk/dD of the part's profile,
+// kexp.hpp: K_p itself for SquaredExp), dK/dsigma_n = 2 sigma_n I.
 // Off-diagonal tiles count twice (symmetry).  Per-workgroup partial sums are reduced in a
 // fixed order by a second kernel (deterministic).
 #include <cmath>
@@ -51,10 +52,13 @@ __global__ __launch_bounds__(1024) void mll_terms_kernel(const double* __restric
   }
 }
 
-// partial[bid][slot]: slot layout = for each SE part p: [S_sigma, S_l1..S_ld], then S_wn.
+// partial[bid][slot]: slot layout = for each stationary part p: [S_sigma, S_l1..S_ld], then
+// S_wn.  S_sigma sums mv K_p, S_lk sums mv W_p r_k^2.  MIX: the description has a Matern part
+// (each part's profile from the device table, one scalar branch per part); SE-only
+// descriptions launch MIX = false, the kernel they always launched.
 // EXACT: d == D (no per-feature bound checks).  Branch-free inner loop: columns past n are
 // clamped to point n - 1 with zero weight, K_p by the K-assembly's table exponential.
-template <int D, bool EXACT>
+template <int D, bool EXACT, bool MIX>
 __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const double* __restrict__ X,
                                                              int n, const double* __restrict__ Kinv,
                                                              size_t ldk, const double* __restrict__ alpha,
@@ -107,6 +111,7 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
     // distance and exponential instead of in front of its weight)
     const size_t irc = (size_t)min(i, n - 1);
     double kin = Kinv[irc + (size_t)min(j0 + wv, n - 1) * ldk];
+    kprof_dispatch<MIX>(MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0, [&](auto pf) {
 #pragma unroll 1
     for (int c = 0; c < 16; ++c) {
       const int jr = j0 + wv + 4 * c;
@@ -128,17 +133,21 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
         }
       }
       const double dist = (dpart[0] + dpart[1]) + (dpart[2] + dpart[3]);
-      const double Kp = kexp_s2(dist, ts) + (i == j ? kp.eps : 0.0);
+      double Wp;
+      const double Kp = kprof_s2_w<decltype(pf)::value>(dist, ts, &Wp) + (i == j ? kp.eps : 0.0);
       const double mk = mv * Kp;
       acc_s += mk;
+      // (SquaredExp: W = K_p, and eps meets r = 0 only -- the weight it always had)
+      const double mw = decltype(pf)::value == 0 ? mk : mv * Wp;
 #pragma unroll
       for (int k = 0; k < D; ++k) {
         if (EXACT || k < d) {
           const double r = xr[k] - xc[k];
-          acc_l[k] = fma(mk, r * r, acc_l[k]);
+          acc_l[k] = fma(mw, r * r, acc_l[k]);
         }
       }
     }
+    });
     // workgroup reduction of (acc_s, acc_l[0..d)) -> partial slots
     for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
 #pragma unroll
@@ -166,7 +175,8 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
 
 // The same pass for d > 32, where the row point and its d sums no longer fit in registers.  Per
 // SE part and 64 x 64 tile, two phases:
-//  1. each thread's 16 weights mk_c = w (alpha_a alpha_b - Kinv_ab) K_p,ab, the distance by a
+//  1. each thread's 16 weights mk_c = w (alpha_a alpha_b - Kinv_ab) W_p,ab (K_p,ab for
+//     SquaredExp; S_sigma sums the K_p ones), the distance by a
 //     run-time loop over all d (row point from global memory / L1, column point wave-uniform);
 //     the Kinv tile is read once per part; the 16 values go to the thread's own LDS slots (no
 //     barrier: each thread reads back only what it wrote) -- held in a register array they
@@ -177,6 +187,7 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
 //     reduced as in mll_grad_tiles_kernel into slots 1 + 32 chunk + k.
 // S_sigma and the WhiteNoise slot are written once.  Same slot layout, same reduction kernel.
 constexpr int GW = 32;
+template <bool MIX>
 __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const double* __restrict__ X,
                                                             int n, const double* __restrict__ Kinv,
                                                             size_t ldk, const double* __restrict__ alpha,
@@ -215,6 +226,7 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
     const double* l2p = kp.l2 + (size_t)p * d;
     // phase 1: the 16 weights
     double acc_s = 0.0;
+    kprof_dispatch<MIX>(MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0, [&](auto pf) {
 #pragma unroll 1
     for (int c = 0; c < 16; ++c) {
       const int jr = j0 + wv + 4 * c;
@@ -237,11 +249,13 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
         dpart[k & 3] = fma(l2p[k], r * r, dpart[k & 3]);
       }
       const double dist = (dpart[0] + dpart[1]) + (dpart[2] + dpart[3]);
-      const double Kp = kexp_s2(dist, ts) + (i == j ? kp.eps : 0.0);
+      double Wp;
+      const double Kp = kprof_s2_w<decltype(pf)::value>(dist, ts, &Wp) + (i == j ? kp.eps : 0.0);
       const double mk = mv * Kp;
-      mks[c][threadIdx.x] = mk;
+      mks[c][threadIdx.x] = decltype(pf)::value == 0 ? mk : mv * Wp;  // phase 2's weight
       acc_s += mk;
     }
+    });
     for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
     // phase 2: the length-scale sums, GW dimensions at a time
     for (int k0 = 0; k0 < d; k0 += GW) {
@@ -307,11 +321,18 @@ __global__ void reduce_partials_kernel(const double* __restrict__ partial, int n
 template <int D>
 int launch_grad_tiles(gpr_ctx* ctx, const KParams& kp, const double* X, int n, const double* Kinv,
                       int ldk, const double* alpha, double* partial, int nslot, long long nblk) {
-  if (kp.d == D)
-    mll_grad_tiles_kernel<D, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+  if (kp.mix) {
+    if (kp.d == D)
+      mll_grad_tiles_kernel<D, true, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+          kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
+    else
+      mll_grad_tiles_kernel<D, false, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+          kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
+  } else if (kp.d == D)
+    mll_grad_tiles_kernel<D, true, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
         kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
   else
-    mll_grad_tiles_kernel<D, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+    mll_grad_tiles_kernel<D, false, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
         kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
   LAUNCH_CHECK(ctx);
   return 0;
@@ -355,8 +376,12 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
     else if (d <= 16) GPR_TRY(launch_grad_tiles<16>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else if (d <= 32) GPR_TRY(launch_grad_tiles<32>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else {
-      mll_grad_wide_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, dX, n, dKinv, (size_t)ldk,
-                                                                    dalpha, partial, nslot);
+      if (kp.mix)
+        mll_grad_wide_kernel<true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+            kp, dX, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
+      else
+        mll_grad_wide_kernel<false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+            kp, dX, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
       LAUNCH_CHECK(ctx);
     }
   }
@@ -369,7 +394,7 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   int off = 0, se = 0;
   bool noise_seen = false;
   for (int t = 0; t < nk; ++t) {
-    if (kinds[t] == GPR_SE) {
+    if (kinds[t] != GPR_WN) {
       const double* ss = s.data() + se * (d + 1);
       const double sig = hp[off];
       grad[off] = -0.5 * (2.0 / std::fabs(sig)) * ss[0];

@@ -16,6 +16,8 @@ from .core import (
     GPRSplitPredictCache,
     LogScale,
     MarginalLikelihood,
+    Matern32,
+    Matern52,
     MllGradCache,
     MllLossCache,
     NoLogScale,

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GPR_SE, GPR_WN, GprError, PosDefException, lib
+from ._lib import GPR_M32, GPR_M52, GPR_SE, GPR_WN, GprError, PosDefException, lib
 
 F64 = torch.float64
 EPS_DEFAULT = 1e-8
@@ -138,6 +138,38 @@ class SquaredExp(AbstractKernel):
         return "SquaredExp()"
 
 
+class Matern32(AbstractKernel):
+    """K(x,x') = sigma^2 (1 + sqrt(3) r) exp(-sqrt(3) r), r = |l * (x - x')|, hp = [sigma,
+    l_1..l_d] as SquaredExp.  The l_k are multipliers (inverse length-scales), following the
+    reference's SquaredExp (exp(-D), no 1/2): the textbook Matern length-scale is 1 / l_k."""
+    KIND = GPR_M32
+
+    def __eq__(self, o):
+        return isinstance(o, Matern32)
+
+    def __hash__(self):
+        return hash("M32")
+
+    def __repr__(self):
+        return "Matern32()"
+
+
+class Matern52(AbstractKernel):
+    """K(x,x') = sigma^2 (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r), r = |l * (x - x')|, hp =
+    [sigma, l_1..l_d] as SquaredExp.  The l_k are multipliers (inverse length-scales), following
+    the reference's SquaredExp (exp(-D), no 1/2): the textbook Matern length-scale is 1 / l_k."""
+    KIND = GPR_M52
+
+    def __eq__(self, o):
+        return isinstance(o, Matern52)
+
+    def __hash__(self):
+        return hash("M52")
+
+    def __repr__(self):
+        return "Matern52()"
+
+
 class WhiteNoise(AbstractKernel):
     """sigma_n^2 I on a same-object diagonal, hp = [sigma_n] (src/covariance.jl:17,60-64)."""
     KIND = GPR_WN
@@ -165,9 +197,29 @@ class ComposedKernel(AbstractKernel):
         return " + ".join(repr(k) for k in self.kernels)
 
 
+def is_stationary(k: AbstractKernel) -> bool:
+    """SquaredExp, Matern32, Matern52: a radial profile of the ARD-scaled distance, hp =
+    [sigma, l_1..l_d].  Every rule the reference states "per SquaredExp part" holds per
+    stationary part."""
+    return k.KIND != GPR_WN
+
+
 def dim_hp(cov: AbstractKernel, dim: int) -> int:
     """src/covariance.jl:27,60; src/compose_covar.jl:26-28."""
-    return sum(dim + 1 if k.KIND == GPR_SE else 1 for k in cov.parts())
+    return sum(dim + 1 if is_stationary(k) else 1 for k in cov.parts())
+
+
+def find_idx(cov: AbstractKernel, i: int, dim: int) -> Tuple[int, int, int]:
+    """find_idx (src/compose_covar.jl:109-115): the part that owns the 1-based hyperparameter
+    index i, as (part index, 1-based index inside the part, 0-based offset of the part's first
+    hyperparameter).  A stationary part owns dim + 1 entries, WhiteNoise one."""
+    off = 0
+    for p, k in enumerate(cov.parts()):
+        w = dim + 1 if is_stationary(k) else 1
+        if off < i <= off + w:
+            return p, i - off, off
+        off += w
+    raise IndexError(f"hyperparameter index {i} out of 1..{off}")
 
 
 class UniformScaling:
@@ -269,9 +321,9 @@ def kernel(cov: AbstractKernel, hp, x, xp=None, eps: float = EPS_DEFAULT,
            ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, host: bool = True):
     """kernel(cov, hp, x[, xp]) -> N x M matrix.
 
-    ``xp is None`` is the 4-arg kernel!(K, cov, hp, x): eps per SE part plus the noise of a
-    WhiteNoise part (src/compose_covar.jl:73-77).  ``xp is x`` is the 5-arg call with
-    `x === xp`: eps per SE part, no noise (src/compose_covar.jl:47-61,
+    ``xp is None`` is the 4-arg kernel!(K, cov, hp, x): eps per stationary part plus the noise
+    of a WhiteNoise part (src/compose_covar.jl:73-77).  ``xp is x`` is the 5-arg call with
+    `x === xp`: eps per stationary part, no noise (src/compose_covar.jl:47-61,
     src/covariance.jl:52-56).  Any other xp is a cross kernel."""
     ctx = ctx or default_context()
     dx = ctx.colmajor(x)
@@ -299,12 +351,12 @@ def kernel_grad(cov: AbstractKernel, i: int, hp, x, eps: float = EPS_DEFAULT,
     hp = np.asarray(hp, dtype=np.float64)
     dim = np.asarray(x).shape[0]
     # WhiteNoise part -> UniformScaling like the reference
-    off = 0
-    for k in cov.parts():
-        w = dim + 1 if k.KIND == GPR_SE else 1
-        if off < i <= off + w and k.KIND == GPR_WN:
+    try:
+        part, _, off = find_idx(cov, i, dim)
+        if cov.parts()[part].KIND == GPR_WN:
             return UniformScaling(2.0 * hp[off])
-        off += w
+    except IndexError:
+        pass  # (the library names the bad index)
     dx = ctx.colmajor(x)
     n, d = dx.shape
     kinds, nk = _kinds_arr(cov)
@@ -331,8 +383,8 @@ class NoLogScale:
 
 
 def islog(cost, md: GPRModel):
-    """src/cost.jl:4-8: LogScale iff an SE part is present."""
-    return LogScale() if any(k.KIND == GPR_SE for k in md.covar.parts()) else NoLogScale()
+    """src/cost.jl:4-8: LogScale iff a stationary part (SquaredExp there) is present."""
+    return LogScale() if any(is_stationary(k) for k in md.covar.parts()) else NoLogScale()
 
 
 class MllLossCache:
@@ -691,7 +743,7 @@ def _part_hps(cov: AbstractKernel, hp, dim: int):
     hp = np.asarray(hp, dtype=np.float64)
     out, off = [], 0
     for k in cov.parts():
-        w = dim + 1 if k.KIND == GPR_SE else 1
+        w = dim + 1 if is_stationary(k) else 1
         out.append(hp[off:off + w])
         off += w
     return out

@@ -12,9 +12,9 @@
  * Conventions (all of them Julia's, so a Julia caller passes its arrays unchanged):
  *   - fp64 everywhere; matrices are COLUMN-MAJOR with an explicit leading dimension.
  *   - x is d x n column-major (each sample's d features contiguous), like md.x.
- *   - A kernel is described by `kinds[nk]` (GPR_SE / GPR_WN, in `+` order) and the flat
- *     hyper-parameter vector `hp` (HOST pointer) of length sum(dim_hp) -- SE: d+1
- *     ([sigma, l_1..l_d]), WN: 1 ([sigma_n]) -- exactly split(hp, dims)
+ *   - A kernel is described by `kinds[nk]` (GPR_SE / GPR_M32 / GPR_M52 / GPR_WN, in `+` order)
+ *     and the flat hyper-parameter vector `hp` (HOST pointer) of length sum(dim_hp) -- SE, M32,
+ *     M52: d+1 ([sigma, l_1..l_d]), WN: 1 ([sigma_n]) -- exactly split(hp, dims)
  *     (src/compose_covar.jl:21-28).
  *   - Pointers named d* are DEVICE pointers (from gpr_malloc, hipMalloc, or a torch
  *     tensor); all other pointers are host pointers.  No pointer is retained after a call
@@ -39,6 +39,8 @@ extern "C" {
 
 #define GPR_SE 1 /* SquaredExp  src/covariance.jl:15 */
 #define GPR_WN 2 /* WhiteNoise  src/covariance.jl:17 */
+#define GPR_M32 3 /* Matern-3/2 (no counterpart in the reference: defined below) */
+#define GPR_M52 4 /* Matern-5/2 */
 
 #define GPR_OK 0
 #define GPR_E_ARG (-1)      /* bad argument (message names it)                      */
@@ -46,9 +48,32 @@ extern "C" {
 #define GPR_E_NOMEM (-3)    /* device allocation failed                             */
 #define GPR_E_UNSUP (-4)    /* unsupported configuration (e.g. an eigen-reduction size) */
 
-/* Kernel descriptions (kinds, nk, hp, d) have the reference's envelope: any input dimension
- * d >= 1 and any number of SquaredExp / WhiteNoise parts (src/covariance.jl:85-95,
- * src/compose_covar.jl:9-28,47-61). */
+/* Kernel descriptions (kinds, nk, hp, d): any input dimension d >= 1 and any number of parts,
+ * in any order, with at least one stationary part (GPR_SE, GPR_M32, GPR_M52).  For SquaredExp /
+ * WhiteNoise parts this is the reference's envelope (src/covariance.jl:85-95,
+ * src/compose_covar.jl:9-28,47-61).
+ *
+ * The stationary parts share one hp layout, [sigma, l_1..l_d], and one distance: with
+ *   D = sum_k (l_k (x_k - x'_k))^2,   r = sqrt(max(D, 0)),
+ *   GPR_SE   k = sigma^2 exp(-D)                                          (the reference's)
+ *   GPR_M32  k = sigma^2 (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *   GPR_M52  k = sigma^2 (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
+ * The l_k are MULTIPLIERS (inverse length-scales), as in the reference's SquaredExp (exp(-D),
+ * no 1/2): the textbook Matern length-scale is 1 / l_k.  Derivatives follow the shape of
+ * src/deriv_covar.jl:20-29 with W = -dk/dD (finite at r = 0):
+ *   dK/dsigma = (2 / |sigma|) K_p   (K_p with eps on a same-object diagonal, as for SE)
+ *   dK/dl_k   = -2 l_k W (x_k - x'_k)^2 on raw x,
+ *   W_SE = k,  W_M32 = sigma^2 (3/2) exp(-sqrt(3) r),
+ *   W_M52 = sigma^2 (5/6) (1 + sqrt(5) r) exp(-sqrt(5) r).
+ * Every rule the reference states per SquaredExp part holds per stationary part: eps once per
+ * stationary part on a same-object diagonal, the noise of the first WhiteNoise, the diagonal-
+ * variance prior sum over ALL parts of hp_part[1]^2, LogScale when a stationary part is present.
+ *
+ * Calls built on SquaredExp's separability or its closed-form erf integrals refuse a description
+ * with a Matern part -- GPR_E_UNSUP, the message names the part, nothing is computed or written:
+ * gpr_split_predict, gpr_split_predict_rows, gpr_split_predict_shard, gpr_split_predict_mgpu,
+ * gpr_split_factors, gpr_integrate, gpr_integrate_noise.  (gpr_antideriv_se takes no kinds: it
+ * is SquaredExp's integral of whatever hp it is given.) */
 
 /* predict modes (src/predict.jl:14-25) */
 #define GPR_PREDICT_MEAN 0  /* predict_mean  src/predict.jl:6-12                     */
@@ -107,6 +132,9 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         runtime-d tile); 20: the difference form for every d > 20
  *   GPR_KBUILD_COLSTORE 1 single-part (SE) upper builds store 1-KB column segments through LDS;
  *                         0: the MFMA D layout (4 columns x 128 B per store instruction)
+ *   GPR_KBUILD_TILES   0  1: a single SquaredExp part's symmetric K by the mirrored 64 x 64 tiles
+ *                         every other description takes, instead of its column build (A/B runs:
+ *                         bench_matern.py times SE and Matern through the same kernels)
  *   GPR_CV_BATCH       1  gpr_cv_batch: every fold in one batched launch; 0: per fold
  *   GPR_CV_BATCH_GB   16  device-memory budget of one batched cross-validation launch
  *   GPR_CV_STREAMS     4  child contexts of the per-fold / per-column paths (<= 8)
@@ -134,9 +162,9 @@ int gpr_timing_reset(gpr_ctx_t ctx);
 /* ---- a2/a3: kernel matrices --------------------------------------------------------- */
 /* `same` argument of gpr_kernel: which of the reference's kernel! forms is meant.        */
 #define GPR_CROSS 0       /* kernel!(K, cov, hp, x, xp), x !== xp: no eps, no noise         */
-#define GPR_SELF 1        /* kernel!(K, cov, hp, x) (4-arg): eps per SE part + sigma_n^2 of  */
+#define GPR_SELF 1        /* kernel!(K, cov, hp, x) (4-arg): eps per stationary part + sigma_n^2 of */
                           /* the first WhiteNoise part (add_noise!, src/compose_covar.jl:73) */
-#define GPR_SAME_OBJECT 2 /* kernel!(K, cov, hp, x, xp) with x === xp (5-arg): eps per SE  */
+#define GPR_SAME_OBJECT 2 /* kernel!(K, cov, hp, x, xp) with x === xp (5-arg): eps per stationary */
                           /* part, NO noise (src/compose_covar.jl:47-61, covariance.jl:52-56)*/
 
 /* K[n x m] (ldk) = kernel(cov, hp, x, xp).  same = GPR_SELF or GPR_SAME_OBJECT: dXp is
@@ -150,7 +178,8 @@ int gpr_kernel(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                const double* dX, int n, const double* dXp, int m, int same, double eps,
                double* dK, int ldk);
 
-/* a4: dK/dtheta_i (1-based i) materialised, n x n.  WN part: writes 2*sigma_n*I.
+/* a4: dK/dtheta_i (1-based i) materialised, n x n.  WN part: writes 2*sigma_n*I; a stationary
+ * part: the rules above with its own W.
  * Replaces grad!(::SquaredExp, DK, i, hp, x, K) src/deriv_covar.jl:20-32 and the
  * composed index mapping src/compose_covar.jl:109-123. */
 int gpr_kernel_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
