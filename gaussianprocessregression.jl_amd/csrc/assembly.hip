@@ -47,6 +47,37 @@ __global__ void scale_inputs_kernel(KParams kp, const double* __restrict__ X, in
   }
 }
 
+// The same for a description with a Periodic part: every part's points are de = 2d wide.
+//   Periodic part:  xs[p][a][k] = l_k cos(2 pi x_k / p_k), xs[p][a][d + k] = l_k sin(2 pi x_k / p_k)
+//                   (sincospi of 2 x / p: pi stays out of the argument), so that the squared
+//                   distance of two embedded points is sum_k (2 l_k sin(pi (x_k - x'_k) / p_k))^2
+//   other parts:    xs[p][a][k] = x_k l_k, xs[p][a][d + k] = 0 (zero features add exact zeros
+//                   to every distance, and zero MFMA k-steps leave the accumulators unchanged)
+// unit: cos / sin without the factor l_k (the gradient pass's per-point buffer).
+__global__ void embed_inputs_kernel(KParams kp, const double* __restrict__ X, int n, int unit,
+                                    double* __restrict__ xs) {
+  const int d = kp.dx, de = kp.de;
+  const size_t total = (size_t)n * d;
+  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total * kp.nse;
+       t += (size_t)gridDim.x * blockDim.x) {
+    const int p = (int)(t / total);
+    const size_t r = t - p * total;
+    const size_t a = r / d;
+    const int k = (int)(r - a * d);
+    const double l = kp.l[(size_t)p * d + k];
+    double* o = xs + ((size_t)p * n + a) * de;
+    if (kp.per[p] != 0.0) {
+      double sn, cs;
+      sincospi((2.0 * X[r]) / kp.pk[(size_t)p * d + k], &sn, &cs);
+      o[k] = unit ? cs : l * cs;
+      o[d + k] = unit ? sn : l * sn;
+    } else {
+      o[k] = X[r] * l;
+      o[d + k] = 0.0;
+    }
+  }
+}
+
 // exp(-D) of the assembly kernels.  GPR_KBUILD_NOEXP (tools/kbuild_bench_noexp only, never
 // the library) swaps in a cheap stand-in to separate exp cost from store cost.
 __device__ __forceinline__ double kexp_neg(double dist) {
@@ -227,17 +258,21 @@ __global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const doubl
 // kernel, which = 0 -> (2/|sigma|) K_p (K_p incl. eps on the diagonal),
 // which = k+1 -> -2 l_k W_p (x_k,a - x_k,b)^2 with RAW x, W = -dk/dD of the part's profile
 // (kexp.hpp; W = K_p without eps for SquaredExp, whose branch is the expression it always was).
+// Periodic part (xs: the embedded points, de wide): which = k+1 <= d ->
+// -2 l_k K (2 sin(pi r_k / p_k))^2, which = d+k+1 -> (4 pi l_k^2 / p_k^2) K r_k sin(2 pi r_k / p_k),
+// r = x_a - x_b on raw x, K without eps (eps meets r = 0 only).
 __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
                              const double* __restrict__ xs, int n, int p, int which,
                              double* __restrict__ DK, size_t ld) {
-  const int d = kp.d;
+  const int d = kp.dx, de = kp.de;
+  const bool per = kp.per && kp.per[p] != 0.0;
   for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < (size_t)n * n;
        t += (size_t)gridDim.x * blockDim.x) {
     const int a = (int)(t % n), b = (int)(t / n);
-    const double* xa = xs + ((size_t)p * n + a) * d;
-    const double* xb = xs + ((size_t)p * n + b) * d;
+    const double* xa = xs + ((size_t)p * n + a) * de;
+    const double* xb = xs + ((size_t)p * n + b) * de;
     double s = 0.0;
-    for (int k = 0; k < d; ++k) {
+    for (int k = 0; k < de; ++k) {
       const double q = xa[k] - xb[k];
       s = fma(q, q, s);
     }
@@ -248,9 +283,18 @@ __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
     if (which == 0) {
       v = (2.0 / fabs(kp.sig[p])) * Kp;
     } else {
-      const int k = which - 1;
+      const int k = (which - 1) % d;
       const double dx = X[(size_t)a * d + k] - X[(size_t)b * d + k];
-      v = -2.0 * kp.l[(size_t)p * d + k] * W * (dx * dx);
+      const double l = kp.l[(size_t)p * d + k];
+      if (!per) {
+        v = -2.0 * l * W * (dx * dx);
+      } else if (which <= d) {
+        const double ch = 2.0 * sinpi(dx / kp.pk[(size_t)p * d + k]);
+        v = -2.0 * l * W * (ch * ch);
+      } else {
+        const double pk = kp.pk[(size_t)p * d + k];
+        v = (4.0 * M_PI * l * l / (pk * pk)) * W * dx * sinpi((2.0 * dx) / pk);
+      }
     }
     DK[(size_t)a + (size_t)b * ld] = v;
   }
@@ -298,11 +342,14 @@ __global__ void set_identity_kernel(double* __restrict__ A, int n, size_t lda) {
 
 int scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double** buf,
                  size_t* cap) {
-  GPR_TRY(ensure_buf(ctx, buf, cap, (size_t)kp.nse * kp.d * n + 1));
-  const size_t total = (size_t)kp.nse * kp.d * n;
+  GPR_TRY(ensure_buf(ctx, buf, cap, (size_t)kp.nse * kp.de * n + 1));
+  const size_t total = (size_t)kp.nse * kp.dx * n;
   int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
   if (blocks < 1) blocks = 1;
-  scale_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, *buf);
+  if (kp.nper)  // (every part 2d features wide)
+    embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 0, *buf);
+  else
+    scale_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, *buf);
   LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1577,11 +1624,14 @@ __global__ __launch_bounds__(256) void pair_kernel(int mode, int d, const double
 
 }  // namespace
 
-int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kp, const double* dX, int n,
+int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kpx, const double* dX, int n,
                          const double* dXp, int m, int same, double* dK, int ldk) {
   if (dK == ctx->kup_ptr) ctx->kup_ptr = nullptr;  // (rebuilt in full)
   if (n <= 0 || (!same && m <= 0)) return 0;
-  GPR_TRY(scale_inputs(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));
+  GPR_TRY(scale_inputs(ctx, kpx, dX, n, &ctx->dxs, &ctx->xs_cap));
+  // everything below works on the scaled (embedded) points: its d is the feature width de, so
+  // the path (compile-time S, upper-only, run-time tile) is chosen by de
+  const KParams kp = kparams_features(kpx);
   if (same) {
     const double el = (double)n * n;
     TimerScope ts(ctx, TC_KBUILD, el * 8.0);  // "flops" slot carries algorithmic bytes
@@ -1600,7 +1650,7 @@ int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kp, const double* dX, int 
     DISPATCH_D(launch_sym, ctx, kp, ctx->dxs, n, dK, ldk);
     LAUNCH_CHECK(ctx);
   } else {
-    GPR_TRY(scale_inputs(ctx, kp, dXp, m, &ctx->dxps, &ctx->xps_cap));
+    GPR_TRY(scale_inputs(ctx, kpx, dXp, m, &ctx->dxps, &ctx->xps_cap));
     TimerScope ts(ctx, TC_OTHER, 0.0);
     if (gram_enabled(ctx, kp.d) && vec_store_ok(dK, ldk))
       return kp.nse > KMAXP ? launch_gram_groups(ctx, kp, ctx->dxs, n, ctx->dxps, m, 0, dK, ldk)
@@ -1611,17 +1661,18 @@ int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kp, const double* dX, int 
   return 0;
 }
 
-int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kp, const double* dX, int n,
+int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kpx, const double* dX, int n,
                                     double* dK, int ldk) {
   ctx->kup_ptr = nullptr;
+  const KParams kp = kparams_features(kpx);  // (paths by the feature width de)
   // upper-only where the tile-DAG will take exactly this matrix directly (potrf_core), with
   // the Gram form (d <= 20) and one or two SquaredExp parts; the full symmetric K otherwise
   // (any description with a Matern part: kmat_symu_kernel is not specialised for them)
   const bool upper = ctx->kbuild_upper && n > 0 && gram_enabled(ctx, kp.d) &&
                      kp.d <= GRAM_CT_MAXD && kp.nse <= 2 && !kp.mix &&
                      dag_takes_whole(ctx, n, ldk, dK) && dag_shape_ok(n, ldk, dK);
-  if (!upper) return launch_kernel_matrix(ctx, kp, dX, n, nullptr, n, 1, dK, ldk);
-  GPR_TRY(scale_inputs(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));
+  if (!upper) return launch_kernel_matrix(ctx, kpx, dX, n, nullptr, n, 1, dK, ldk);
+  GPR_TRY(scale_inputs(ctx, kpx, dX, n, &ctx->dxs, &ctx->xs_cap));
   {
     // bytes written: column c gets min(n, 128 (c / 128 + 1)) rows
     double bytes = 0.0;
@@ -1641,6 +1692,16 @@ int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n
   if (total == 0) return 0;
   int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
   scale_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, out);
+  LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n) {
+  if (!kp.nper || n <= 0) return 0;
+  GPR_TRY(ensure_buf(ctx, &ctx->dxs, &ctx->xs_cap, (size_t)kp.nse * kp.de * n + 1));
+  const size_t total = (size_t)kp.nse * kp.dx * n;
+  const int blocks = (int)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 4096));
+  embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 1, ctx->dxs);
   LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1700,7 +1761,7 @@ int gpr_kernel_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
   // find_idx (src/compose_covar.jl:109-115)
   int off = 0, se = 0;
   for (int t = 0; t < nk; ++t) {
-    const int w = kinds[t] != GPR_WN ? d + 1 : 1;
+    const int w = kind_hp_width(kinds[t], d);
     if (i - 1 < off + w) {
       const int local = i - 1 - off;
       const int blocks = (int)std::min<long long>(((long long)n * n + 255) / 256, 8192);

@@ -14,20 +14,25 @@
 // (kexp.hpp).  SE is the reference's; the two Matern profiles are this library's own.
 enum { KPROF_SE = 0, KPROF_M32 = 1, KPROF_M52 = 2 };
 inline bool kind_stationary(int kind) {
-  return kind == GPR_SE || kind == GPR_M32 || kind == GPR_M52;
+  return kind == GPR_SE || kind == GPR_M32 || kind == GPR_M52 || kind == GPR_PER;
+}
+// hyper-parameters of one part: [sigma, l_1..l_d] (SquaredExp, Matern), [sigma, l_1..l_d,
+// p_1..p_d] (Periodic), [sigma_n] (WhiteNoise)
+inline int kind_hp_width(int kind, int d) {
+  return kind == GPR_WN ? 1 : kind == GPR_PER ? 2 * d + 1 : d + 1;
 }
 inline int kind_profile(int kind) {
   return kind == GPR_M32 ? KPROF_M32 : kind == GPR_M52 ? KPROF_M52 : KPROF_SE;
 }
 inline const char* kind_name(int kind) {
   return kind == GPR_SE ? "SquaredExp" : kind == GPR_M32 ? "Matern32" : kind == GPR_M52 ? "Matern52"
-         : kind == GPR_WN ? "WhiteNoise" : "?";
+         : kind == GPR_PER ? "Periodic" : kind == GPR_WN ? "WhiteNoise" : "?";
 }
 
 // Kernel description passed BY VALUE to every assembly kernel (a few dozen bytes of kernargs;
 // the per-part tables live in the context's parameter block, see KParBlock).
 // Mirrors split(hp, dims) of src/compose_covar.jl:21-28: the stationary parts (SquaredExp,
-// Matern32, Matern52: hp [sigma, l_1..l_d] each) in `+` order
+// Matern32, Matern52: hp [sigma, l_1..l_d] each; Periodic: [sigma, l_1..l_d, p_1..p_d]) in `+` order
 // and the first WhiteNoise part (add_noise! src/compose_covar.jl:63-71).  Any d >= 1 and any
 // number of parts, as the reference.
 struct KParams {
@@ -57,7 +62,25 @@ struct KParams {
   // descriptions launch the SE instantiations
   int prof[KMAXP];
   int mix;
+  // Periodic parts (appended: descriptions without one pass the fields above unchanged).  A
+  // Periodic part is the SquaredExp profile on the 2d embedded features
+  // [l_k cos(2 pi x_k / p_k) | l_k sin(2 pi x_k / p_k)]; in a description that has one every
+  // part's scaled points are de = 2d wide (SquaredExp / Matern parts: l_k x_k, then d zeros).
+  int dx;             // the input dimension, also in a feature view (below), whose d is de
+  int de;             // feature width of dxs / dxps / the Gram operands: 2d with a Periodic part, else d
+  int nper;           // number of Periodic parts
+  const double* per;  // [nse]    1.0 for a Periodic part, else 0.0 (null when nper == 0)
+  const double* pk;   // [nse][d] periods p_k (1.0 for the other parts; null when nper == 0)
 };
+
+// The description as the K-assembly kernels take it: they read kp.d features per scaled point,
+// so their launchers get d = de.  (They read neither l nor l2.)  Without a Periodic part this
+// is kp itself.
+inline KParams kparams_features(const KParams& kp) {
+  KParams f = kp;
+  f.d = kp.de;
+  return f;
+}
 
 // sigma / profile of stationary part p (host side, any p < nse)
 inline double kp_sigma(const KParams& kp, int p, int* prof = nullptr) {
@@ -68,19 +91,18 @@ inline double kp_sigma(const KParams& kp, int p, int* prof = nullptr) {
         if (prof) *prof = kind_profile(kp.kinds[i]);
         return kp.hp[off];
       }
-      off += kp.d + 1;
-    } else {
-      off += 1;
     }
+    off += kind_hp_width(kp.kinds[i], kp.dx);
   }
   if (prof) *prof = KPROF_SE;
   return 0.0;
 }
-// the first part that is not SquaredExp / WhiteNoise (its kind), or 0: the calls that rely on
-// SE's separability or its closed-form integrals refuse such a description (GPR_E_UNSUP)
-inline int kinds_first_matern(const int* kinds, int nk, int* index) {
+// the first part that is not SquaredExp / WhiteNoise (its kind: Matern or Periodic), or 0: the
+// calls that rely on SE's separability or its closed-form integrals refuse such a description
+// (GPR_E_UNSUP)
+inline int kinds_first_non_se(const int* kinds, int nk, int* index) {
   for (int i = 0; i < nk; ++i)
-    if (kinds[i] == GPR_M32 || kinds[i] == GPR_M52) {
+    if (kinds[i] == GPR_M32 || kinds[i] == GPR_M52 || kinds[i] == GPR_PER) {
       if (index) *index = i;
       return kinds[i];
     }
@@ -100,16 +122,21 @@ inline KParams kparams_group(const KParams& kp, int p0, int cnt, int has_noise) 
     g.sigma[p] = p < cnt ? kp_sigma(kp, p0 + p, &g.prof[p]) : 0.0;
     if (g.prof[p] != KPROF_SE) g.mix = 1;
   }
-  g.l = kp.l + (size_t)p0 * kp.d;
-  g.l2 = kp.l2 + (size_t)p0 * kp.d;
+  g.l = kp.l + (size_t)p0 * kp.dx;
+  g.l2 = kp.l2 + (size_t)p0 * kp.dx;
   g.sig = kp.sig + p0;
   g.pf = kp.pf + p0;
+  if (kp.per) {
+    g.per = kp.per + p0;
+    g.pk = kp.pk + (size_t)p0 * kp.dx;
+  }
   return g;
 }
 
 // Per-context parameter block: NSLOT device slots of `cap` doubles ([l | l2 | sigma | profile]
 // of one kernel description each; the profile codes are part of the block, so that the
-// comparison with the description made last tells SquaredExp from Matern at equal hp) and as many pinned host staging slots.  make_kparams fills host
+// comparison with the description made last tells SquaredExp from Matern at equal hp; with a
+// Periodic part [is periodic | p] follow, see make_kparams) and as many pinned host staging slots.  make_kparams fills host
 // slot `next`, uploads it in stream order and records ev[next] -- unless the tables equal those
 // of the description made last, whose slot then serves again; a slot is re-filled only once
 // its previous upload has completed (NSLOT descriptions later: the wait does not block in
@@ -124,6 +151,7 @@ struct KParBlock {
   hipEvent_t ev[NSLOT] = {};
   int last = -1;           // slot of the description made last (its host copy is compared), or -1
   size_t last_need = 0;    // its length in doubles
+  int last_nper = 0;       // its number of Periodic parts (the two block layouts can be equally long)
   std::vector<double> tmp; // the description being made
 };
 
@@ -332,9 +360,9 @@ void copy_knobs(const gpr_ctx* from, gpr_ctx* to);
 
 // the calls built on SquaredExp's separability or its closed-form integrals: GPR_E_UNSUP,
 // naming the part, before anything is computed or written
-inline int refuse_matern(gpr_ctx* ctx, const int* kinds, int nk, const char* what) {
+inline int refuse_non_se(gpr_ctx* ctx, const int* kinds, int nk, const char* what) {
   int idx = 0;
-  const int kind = kinds ? kinds_first_matern(kinds, nk, &idx) : 0;
+  const int kind = kinds ? kinds_first_non_se(kinds, nk, &idx) : 0;
   if (!kind) return 0;
   return set_err(ctx, GPR_E_UNSUP, "%s needs SquaredExp parts: part %d is %s", what, idx + 1,
                  kind_name(kind));
@@ -398,6 +426,10 @@ int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kp, const doubl
                                     double* dK, int ldk);
 int launch_mirror_upper(gpr_ctx* ctx, double* A, int n, int lda);
 int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double* out);
+// ctx->dxs <- per part and point [cos(2 pi x_k / p_k) | sin(2 pi x_k / p_k)] (2d wide, without
+// l_k) for the Periodic parts of kp (the other parts' rows are not for use); the MLL gradient's
+// per-point table
+int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n);
 int launch_pair(gpr_ctx* ctx, int mode, int d, const double* xa, int na, const double* xb, int nb,
                 double s2, double* out, size_t sa, size_t sb);
 int launch_set_identity(gpr_ctx* ctx, double* A, int n, int lda);

@@ -91,18 +91,31 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   if (!hp) return set_err(ctx, GPR_E_ARG, "hp is NULL");
   if (d <= 0) return set_err(ctx, GPR_E_ARG, "d=%d (needs d >= 1)", d);
   memset(kp, 0, sizeof *kp);
-  int nse = 0;
-  for (int i = 0; i < nk; ++i) {
+  int nse = 0, nper = 0;
+  for (int i = 0, off = 0; i < nk; ++i) {
     if (kind_stationary(kinds[i])) ++nse;
     else if (kinds[i] != GPR_WN) return set_err(ctx, GPR_E_ARG, "unknown kernel kind %d", kinds[i]);
+    if (kinds[i] == GPR_PER) {  // (before anything is computed or written)
+      ++nper;
+      for (int k = 0; k < d; ++k) {
+        const double p = hp[off + 1 + d + k];
+        if (!(std::fabs(p) > 0.0) || std::isinf(p))
+          return set_err(ctx, GPR_E_ARG, "part %d (Periodic): period p_%d = %g of dimension %d is "
+                                         "zero or not finite", i + 1, k + 1, p, k + 1);
+      }
+    }
+    off += kind_hp_width(kinds[i], d);
   }
   if (nse == 0)
     return set_err(ctx, GPR_E_ARG, "kernel needs at least one stationary part (SquaredExp, "
-                                   "Matern32 or Matern52)");
+                                   "Matern32, Matern52 or Periodic)");
   // this description's slot of the parameter block:
-  // [l (nse d) | l2 (nse d) | sigma (nse) | profile (nse)]
+  // [l (nse d) | l2 (nse d) | sigma (nse) | profile (nse)], then with a Periodic part
+  // [is periodic (nse) | p (nse d)] -- a longer block, so that it never compares equal to one
+  // without, and two Periodic parts that differ only in p differ in the block
   KParBlock& kb = ctx->kpar;
-  const size_t nl = (size_t)nse * d, need = 2 * nl + 2 * (size_t)nse;
+  const size_t nl = (size_t)nse * d;
+  const size_t need = 2 * nl + 2 * (size_t)nse + (nper ? nl + (size_t)nse : 0);
   if (need > kb.cap || !kb.dev) {
     // (first use, or a description past every earlier one: never inside the 4 x 64 envelope
     // once the block exists)
@@ -130,7 +143,9 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   kb.tmp.resize(need);
   double* hl = kb.tmp.data();
   kp->exptab = ctx->dexptab;
-  kp->d = d;
+  kp->d = kp->dx = d;
+  kp->de = nper ? 2 * d : d;
+  kp->nper = nper;
   kp->eps = eps;
   kp->kinds = kinds;
   kp->nk = nk;
@@ -150,8 +165,14 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
         hl[(size_t)kp->nse * d + k] = hp[off + 1 + k];
         hl[nl + (size_t)kp->nse * d + k] = hp[off + 1 + k] * hp[off + 1 + k];
       }
+      if (nper) {
+        const bool per = kinds[i] == GPR_PER;
+        hl[2 * nl + 2 * nse + kp->nse] = per ? 1.0 : 0.0;
+        for (int k = 0; k < d; ++k)
+          hl[2 * nl + 3 * (size_t)nse + (size_t)kp->nse * d + k] = per ? hp[off + 1 + d + k] : 1.0;
+      }
       kp->nse++;
-      off += d + 1;
+      off += kind_hp_width(kinds[i], d);
     } else {
       if (!kp->has_noise) {  // findfirst(WhiteNoise) -- src/compose_covar.jl:64-68
         kp->has_noise = 1;
@@ -164,7 +185,7 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   // the tables of the description made last on this context (a fit and the gradient or the
   // posterior that follows it share hp): its slot serves again, nothing is uploaded
   int slot = kb.last;
-  if (slot < 0 || kb.last_need != need ||
+  if (slot < 0 || kb.last_need != need || kb.last_nper != nper ||
       memcmp(kb.host + (size_t)slot * kb.cap, hl, need * sizeof(double)) != 0) {
     slot = kb.next;
     kb.next = (slot + 1) % KParBlock::NSLOT;
@@ -177,12 +198,17 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
     HIP_TRY(ctx, hipEventRecord(kb.ev[slot], ctx->stream));
     kb.last = slot;
     kb.last_need = need;
+    kb.last_nper = nper;
   }
   const double* dl = kb.dev + (size_t)slot * kb.cap;
   kp->l = dl;
   kp->l2 = dl + nl;
   kp->sig = dl + 2 * nl;
   kp->pf = dl + 2 * nl + nse;
+  if (nper) {
+    kp->per = dl + 2 * nl + 2 * nse;
+    kp->pk = dl + 2 * nl + 3 * (size_t)nse;
+  }
   if (D_total) *D_total = off;
   return 0;
 }

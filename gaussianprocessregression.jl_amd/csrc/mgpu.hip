@@ -540,7 +540,7 @@ int gpr_split_predict_mgpu(gpr_mgpu_t h, const int* kinds, int nk, const double*
     return mg_err(h, GPR_E_ARG, "fit_mode %d is neither GPR_MGPU_BROADCAST nor _REPLICATE", fit_mode);
   {  // (before any device starts: the split prediction is built on SquaredExp's separability)
     int idx = 0;
-    const int kind = kinds_first_matern(kinds, nk, &idx);
+    const int kind = kinds_first_non_se(kinds, nk, &idx);
     if (kind)
       return mg_err(h, GPR_E_UNSUP, "split prediction needs SquaredExp parts: part %d is %s",
                     idx + 1, kind_name(kind));

@@ -302,6 +302,217 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
     partial[(size_t)bid * nslot + slot] = red[0][GW + 1] + red[1][GW + 1] + red[2][GW + 1] + red[3][GW + 1];
 }
 
+// The pass for a description with a Periodic part, any d: mll_grad_wide_kernel's two phases with
+// one wave-uniform branch per part on "is periodic".  cs: per part and point the unit features
+// [cos a_k | sin a_k], a_k = 2 pi x_k / p_k (launch_embed_unit; 2d wide, only Periodic parts'
+// rows are read) -- no pair evaluates a transcendental but the exponential.
+// Periodic part, slots [S_sigma, S_l1..S_ld, S_p1..S_pd]:
+//  1. D = sum_k l_k^2 chord_k^2, chord_k^2 = (cos a - cos b)^2 + (sin a - sin b)^2
+//     = (2 sin(pi r_k / p_k))^2, GP dimensions at a time; weights mk = mv K_p as for SquaredExp;
+//  2. per chunk of GP = 8 dimensions (row point's x, cos, sin and two sums: 40 doubles; at 16
+//     the unrolled wave-uniform column loads cost 50 more SGPR spills for no fewer passes that
+//     matter):
+//     S_lk += mk chord_k^2, S_pk += mk r_k sin(a_k - b_k), sin(a - b) = sin a cos b - cos a sin b.
+// The other parts run the wide kernel's phases on raw x unchanged (slots [S_sigma, S_l1..S_ld]).
+constexpr int GP = 8;
+template <bool MIX>
+__global__ __launch_bounds__(256) void mll_grad_per_kernel(KParams kp, const double* __restrict__ X,
+                                                           const double* __restrict__ cs, int n,
+                                                           const double* __restrict__ Kinv,
+                                                           size_t ldk, const double* __restrict__ alpha,
+                                                           double* __restrict__ partial, int nslot) {
+  __shared__ double red[4][GW + 2];
+  __shared__ double tabs[KMAXP][256];  // sigma_p^2 2^(j/256)
+  __shared__ double mks[16][256];      // mk_c of every thread
+  const int bid = blockIdx.x;
+  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
+  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
+  while (bj * (bj + 1) / 2 > bid) --bj;
+  const int bi = bid - bj * (bj + 1) / 2;
+  const int i0 = bi * GT, j0 = bj * GT;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int d = kp.dx, de = kp.de;
+  const int i = i0 + lane;
+  const bool irow = i < n;
+  const double wgt = (bi == bj) ? 1.0 : 2.0;
+  const size_t irc = (size_t)min(i, n - 1);
+  const double* xrow = X + irc * d;
+
+  const double ai = irow ? alpha[i] : 0.0;
+  double s_wn = 0.0;
+  if (bi == bj && irow && ((lane - wv) & 3) == 0) s_wn = ai * ai - Kinv[(size_t)i + (size_t)i * ldk];
+
+  int slot = 0;
+  for (int p = 0; p < kp.nse; ++p) {
+    if ((p & (KMAXP - 1)) == 0) {  // this group of parts' exp tables
+      __syncthreads();
+      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)
+        tabs[g - p][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
+      __syncthreads();
+    }
+    const double* ts = tabs[p & (KMAXP - 1)];
+    const double* l2p = kp.l2 + (size_t)p * d;
+    const bool per = __builtin_amdgcn_readfirstlane((int)kp.per[p]) != 0;
+    const double* csp = cs + (size_t)p * n * de;  // this part's unit features
+    const double* crow = csp + irc * de;
+    // phase 1: the 16 weights.  A Periodic part's 16 distances first, GP dimensions of the row
+    // point's cos / sin in registers at a time (the row point is read once per chunk, not once
+    // per column), accumulated in the thread's own mks slots
+    if (per) {
+      for (int k0 = 0; k0 < d; k0 += GP) {
+        const int kn = min(GP, d - k0);  // wave-uniform
+        double cr[GP], sr[GP];
+#pragma unroll
+        for (int k = 0; k < GP; ++k) {
+          cr[k] = k < kn ? crow[k0 + k] : 0.0;
+          sr[k] = k < kn ? crow[d + k0 + k] : 0.0;
+        }
+#pragma unroll 1
+        for (int c = 0; c < 16; ++c) {
+          const int j = min(j0 + wv + 4 * c, n - 1);
+          const double* cc = csp + (size_t)j * de + k0;
+          double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+          for (int k = 0; k < GP; ++k) {
+            const double cb = k < kn ? cc[k] : 0.0, sb = k < kn ? cc[d + k] : 0.0;
+            const double l2 = k < kn ? l2p[k0 + k] : 0.0;
+            const double dc = cr[k] - cb, ds = sr[k] - sb;
+            if (k & 1) a1 = fma(l2, fma(dc, dc, ds * ds), a1);
+            else a0 = fma(l2, fma(dc, dc, ds * ds), a0);
+          }
+          const double prev = k0 ? mks[c][threadIdx.x] : 0.0;
+          mks[c][threadIdx.x] = prev + (a0 + a1);
+        }
+      }
+    }
+    double acc_s = 0.0;
+    kprof_dispatch<MIX>(MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0, [&](auto pf) {
+#pragma unroll 1
+    for (int c = 0; c < 16; ++c) {
+      const int jr = j0 + wv + 4 * c;
+      const int j = min(jr, n - 1);  // wave-uniform: scalar loads of the point
+      const double kin = Kinv[irc + (size_t)j * ldk];
+      const double mv = (irow && jr < n) ? wgt * (ai * alpha[j] - kin) : 0.0;
+      double dist;
+      if (per) {
+        dist = mks[c][threadIdx.x];
+      } else {
+        double dpart[4] = {0.0, 0.0, 0.0, 0.0};
+        const double* xc = X + (size_t)j * d;
+#pragma unroll 1
+        for (int k = 0; k < d; ++k) {
+          const double r = xrow[k] - xc[k];
+          dpart[k & 3] = fma(l2p[k], r * r, dpart[k & 3]);
+        }
+        dist = (dpart[0] + dpart[1]) + (dpart[2] + dpart[3]);
+      }
+      double Wp;
+      const double Kp = kprof_s2_w<decltype(pf)::value>(dist, ts, &Wp) + (i == j ? kp.eps : 0.0);
+      const double mk = mv * Kp;
+      mks[c][threadIdx.x] = decltype(pf)::value == 0 ? mk : mv * Wp;  // phase 2's weight
+      acc_s += mk;
+    }
+    });
+    for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
+    if (per) {
+      // phase 2, Periodic: both sums of GP dimensions at a time
+      for (int k0 = 0; k0 < d; k0 += GP) {
+        const int kn = min(GP, d - k0);  // wave-uniform
+        double xr[GP], cr[GP], sr[GP], acc_l[GP], acc_p[GP];
+#pragma unroll
+        for (int k = 0; k < GP; ++k) {
+          xr[k] = k < kn ? xrow[k0 + k] : 0.0;
+          cr[k] = k < kn ? crow[k0 + k] : 0.0;
+          sr[k] = k < kn ? crow[d + k0 + k] : 0.0;
+          acc_l[k] = acc_p[k] = 0.0;
+        }
+#pragma unroll 1
+        for (int c = 0; c < 16; ++c) {
+          const int j = min(j0 + wv + 4 * c, n - 1);
+          const double* xc = X + (size_t)j * d + k0;
+          const double* cc = csp + (size_t)j * de + k0;
+          const double mk = mks[c][threadIdx.x];
+#pragma unroll
+          for (int k = 0; k < GP; ++k) {
+            const double cb = k < kn ? cc[k] : 0.0, sb = k < kn ? cc[d + k] : 0.0;
+            const double r = xr[k] - (k < kn ? xc[k] : 0.0);
+            const double dc = cr[k] - cb, ds = sr[k] - sb;
+            acc_l[k] = fma(mk, fma(dc, dc, ds * ds), acc_l[k]);
+            acc_p[k] = fma(mk * r, fma(sr[k], cb, -(cr[k] * sb)), acc_p[k]);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < GP; ++k)
+          for (int o = 32; o > 0; o >>= 1) {
+            acc_l[k] += __shfl_xor(acc_l[k], o);
+            acc_p[k] += __shfl_xor(acc_p[k], o);
+          }
+        __syncthreads();
+        if (lane == 0) {
+          red[wv][0] = acc_s;
+#pragma unroll
+          for (int k = 0; k < GP; ++k) {
+            red[wv][1 + k] = acc_l[k];
+            red[wv][1 + GP + k] = acc_p[k];
+          }
+        }
+        __syncthreads();
+        // slot 0 of the part (S_sigma) with the first chunk, then this chunk's kn + kn sums
+        for (int t = threadIdx.x + (k0 ? 1 : 0); t < 1 + 2 * GP; t += 256) {
+          const int k = t == 0 ? 0 : (t - 1) % GP;
+          if (t > 0 && k >= kn) continue;
+          const int dst = t == 0 ? 0 : t <= GP ? 1 + k0 + k : 1 + d + k0 + k;
+          partial[(size_t)bid * nslot + slot + dst] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+        }
+      }
+      slot += 2 * d + 1;
+      continue;
+    }
+    // phase 2: the length-scale sums, GW dimensions at a time
+    for (int k0 = 0; k0 < d; k0 += GW) {
+      const int kn = min(GW, d - k0);  // wave-uniform
+      double xr[GW], acc_l[GW];
+#pragma unroll
+      for (int k = 0; k < GW; ++k) {
+        xr[k] = k < kn ? xrow[k0 + k] : 0.0;
+        acc_l[k] = 0.0;
+      }
+#pragma unroll 1
+      for (int c = 0; c < 16; ++c) {
+        const int j = min(j0 + wv + 4 * c, n - 1);
+        const double* xc = X + (size_t)j * d + k0;
+        const double mk = mks[c][threadIdx.x];
+#pragma unroll
+        for (int k = 0; k < GW; ++k) {
+          const double r = xr[k] - (k < kn ? xc[k] : 0.0);
+          acc_l[k] = fma(mk, r * r, acc_l[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < GW; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc_l[k] += __shfl_xor(acc_l[k], o);
+      __syncthreads();
+      if (lane == 0) {
+        red[wv][0] = acc_s;
+#pragma unroll
+        for (int k = 0; k < GW; ++k) red[wv][1 + k] = acc_l[k];
+      }
+      __syncthreads();
+      for (int t = threadIdx.x + (k0 ? 1 : 0); t < kn + 1; t += 256)
+        partial[(size_t)bid * nslot + slot + (t ? k0 + t : 0)] =
+            red[0][t] + red[1][t] + red[2][t] + red[3][t];
+    }
+    slot += d + 1;
+  }
+  for (int o = 32; o > 0; o >>= 1) s_wn += __shfl_xor(s_wn, o);
+  __syncthreads();
+  if (lane == 0) red[wv][GW + 1] = s_wn;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partial[(size_t)bid * nslot + slot] = red[0][GW + 1] + red[1][GW + 1] + red[2][GW + 1] + red[3][GW + 1];
+}
+
 // out[slot] = sum_b partial[b][slot]  (fixed order)
 __global__ void reduce_partials_kernel(const double* __restrict__ partial, int nblk, int nslot,
                                        double* __restrict__ out) {
@@ -364,13 +575,23 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   if (n <= 0 || ldk < n || !dX || !dKinv || !dalpha || !grad) return set_err(ctx, GPR_E_ARG, "bad args");
   const int nt = (n + GT - 1) / GT;
   const long long nblk = (long long)nt * (nt + 1) / 2;
-  const int nslot = kp.nse * (d + 1) + 1;
+  // per stationary part its hp width (d + 1; Periodic 2d + 1), then the WhiteNoise slot
+  const int nslot = kp.nse * (d + 1) + kp.nper * d + 1;
   GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, (size_t)nblk * nslot + nslot + 64));
   double* partial = ctx->dscratch;
   double* sums = ctx->dscratch + (size_t)nblk * nslot;
   {
     TimerScope ts(ctx, TC_OTHER, 0.0);
-    if (d <= 2) GPR_TRY(launch_grad_tiles<2>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
+    if (kp.nper) {
+      GPR_TRY(launch_embed_unit(ctx, kp, dX, n));
+      if (kp.mix)
+        mll_grad_per_kernel<true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+            kp, dX, ctx->dxs, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
+      else
+        mll_grad_per_kernel<false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
+            kp, dX, ctx->dxs, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
+      LAUNCH_CHECK(ctx);
+    } else if (d <= 2) GPR_TRY(launch_grad_tiles<2>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else if (d <= 4) GPR_TRY(launch_grad_tiles<4>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else if (d <= 8) GPR_TRY(launch_grad_tiles<8>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
     else if (d <= 16) GPR_TRY(launch_grad_tiles<16>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
@@ -391,16 +612,21 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   HIP_TRY(ctx, hipMemcpyAsync(s.data(), sums, nslot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // assemble in hp order (kinds order)
-  int off = 0, se = 0;
+  int off = 0, so = 0;
   bool noise_seen = false;
   for (int t = 0; t < nk; ++t) {
     if (kinds[t] != GPR_WN) {
-      const double* ss = s.data() + se * (d + 1);
+      const double* ss = s.data() + so;
       const double sig = hp[off];
       grad[off] = -0.5 * (2.0 / std::fabs(sig)) * ss[0];
       for (int k = 0; k < d; ++k) grad[off + 1 + k] = -0.5 * (-2.0 * hp[off + 1 + k]) * ss[1 + k];
-      off += d + 1;
-      ++se;
+      if (kinds[t] == GPR_PER)  // dK/dp_k = (4 pi l_k^2 / p_k^2) K r_k sin(2 pi r_k / p_k)
+        for (int k = 0; k < d; ++k) {
+          const double l = hp[off + 1 + k], pk = hp[off + 1 + d + k];
+          grad[off + 1 + d + k] = -0.5 * (4.0 * M_PI * l * l / (pk * pk)) * ss[1 + d + k];
+        }
+      off += kind_hp_width(kinds[t], d);
+      so += kind_hp_width(kinds[t], d);
     } else {
       // every WhiteNoise part's gradient is 2 sigma_n I (src/deriv_covar.jl:31-32)
       grad[off] = -0.5 * (2.0 * hp[off]) * s[nslot - 1];

@@ -134,7 +134,7 @@ double diag_prior(const int* kinds, int nk, const double* hp, int d) {
   int off = 0;
   for (int t = 0; t < nk; ++t) {
     s += hp[off] * hp[off];
-    off += kinds[t] != GPR_WN ? d + 1 : 1;
+    off += kind_hp_width(kinds[t], d);
   }
   return s;
 }
@@ -477,7 +477,7 @@ int gpr_integrate(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int
                   const double* b, double eps, double* dK, int ldk, double* dwt, double* Iout,
                   double* var) {
   if (!a || !b || !Iout || !var || !dwt || ny <= 0) return set_err(ctx, GPR_E_ARG, "bad args");
-  GPR_TRY(refuse_matern(ctx, kinds, nk, "gpr_integrate (erf antiderivatives)"));
+  GPR_TRY(refuse_non_se(ctx, kinds, nk, "gpr_integrate (erf antiderivatives)"));
   // update_cache!(wc, md, hp, nothing) (:64-69): K, cholesky!, wt = K^{-1} y
   int hinfo = 0;
   const int rc = gpr_fit(ctx, kinds, nk, hp, d, dX, n, dy, ny, ldy, eps, dK, ldk, dwt, &hinfo);
@@ -1220,7 +1220,7 @@ int gpr_integrate_noise(gpr_ctx_t ctx, const int* kinds, int nk, const double* h
                         const double* a, const double* b, const double* noise, double eps,
                         double* Iout, double* var) {
   KParams kp;
-  GPR_TRY(refuse_matern(ctx, kinds, nk, "gpr_integrate_noise (erf antiderivatives)"));
+  GPR_TRY(refuse_non_se(ctx, kinds, nk, "gpr_integrate_noise (erf antiderivatives)"));
   GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, nullptr));
   if (n <= 0 || ny <= 0 || ldy < n || !dX || !dy || !a || !b || !noise || !Iout || !var)
     return set_err(ctx, GPR_E_ARG, "bad args");
@@ -1301,7 +1301,7 @@ int gpr_split_factors(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
                       const double* dX, int ns, const double* dXe, int ne, const double* dXq,
                       int nq, int part, double* dA, double* dB, double* dC) {
   KParams kp;
-  GPR_TRY(refuse_matern(ctx, kinds, nk, "gpr_split_factors (separable kernel)"));
+  GPR_TRY(refuse_non_se(ctx, kinds, nk, "gpr_split_factors (separable kernel)"));
   GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, 0.0, &kp, nullptr));
   if (part < 0 || part >= kp.nse) return set_err(ctx, GPR_E_ARG, "part out of range");
   const size_t need = (size_t)kp.nse * d * (ns + ne + nq);
@@ -1410,7 +1410,7 @@ int split_predict_pieces(gpr_ctx* ctx, const int* kinds, int nk, const double* h
                          int npieces, int var_lo, int var_hi, double eps, double* dmu, int ldmu,
                          double* dvar, bool compact) {
   KParams kp;
-  GPR_TRY(refuse_matern(ctx, kinds, nk, "split prediction (separable kernel)"));
+  GPR_TRY(refuse_non_se(ctx, kinds, nk, "split prediction (separable kernel)"));
   GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, nullptr));
   if (ns <= 0 || ne <= 0 || nq <= 0 || ldu < ns || !dX || !dU || !dwt || !dXe || !dXq || !dmu ||
       !dvar || npieces < 0 || (npieces && !pieces))

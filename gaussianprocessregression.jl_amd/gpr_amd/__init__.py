@@ -18,6 +18,9 @@ from .core import (
     MarginalLikelihood,
     Matern32,
     Matern52,
+    Periodic,
+    is_stationary,
+    part_dim_hp,
     MllGradCache,
     MllLossCache,
     NoLogScale,

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GPR_M32, GPR_M52, GPR_SE, GPR_WN, GprError, PosDefException, lib
+from ._lib import GPR_M32, GPR_M52, GPR_PER, GPR_SE, GPR_WN, GprError, PosDefException, lib
 
 F64 = torch.float64
 EPS_DEFAULT = 1e-8
@@ -170,6 +170,23 @@ class Matern52(AbstractKernel):
         return "Matern52()"
 
 
+class Periodic(AbstractKernel):
+    """K(x,x') = sigma^2 exp(-sum_k (2 l_k sin(pi (x_k - x'_k) / p_k))^2), hp = [sigma, l_1..l_d,
+    p_1..p_d] (2d + 1 values).  MacKay's periodic kernel as a product over dimensions; the l_k
+    are multipliers as for SquaredExp (textbook length-scale 1 / (sqrt(2) l_k)), K is even in
+    every period p_k, and a period that is zero or not finite is refused."""
+    KIND = GPR_PER
+
+    def __eq__(self, o):
+        return isinstance(o, Periodic)
+
+    def __hash__(self):
+        return hash("PER")
+
+    def __repr__(self):
+        return "Periodic()"
+
+
 class WhiteNoise(AbstractKernel):
     """sigma_n^2 I on a same-object diagonal, hp = [sigma_n] (src/covariance.jl:17,60-64)."""
     KIND = GPR_WN
@@ -199,23 +216,31 @@ class ComposedKernel(AbstractKernel):
 
 def is_stationary(k: AbstractKernel) -> bool:
     """SquaredExp, Matern32, Matern52: a radial profile of the ARD-scaled distance, hp =
-    [sigma, l_1..l_d].  Every rule the reference states "per SquaredExp part" holds per
-    stationary part."""
+    [sigma, l_1..l_d]; Periodic: hp = [sigma, l_1..l_d, p_1..p_d].  Every rule the reference
+    states "per SquaredExp part" holds per stationary part."""
     return k.KIND != GPR_WN
+
+
+def part_dim_hp(k: AbstractKernel, dim: int) -> int:
+    """Hyperparameters of one part: WhiteNoise 1, Periodic 2 dim + 1, the other stationary
+    parts dim + 1.  Every split of a flat hp vector goes through this."""
+    if k.KIND == GPR_WN:
+        return 1
+    return 2 * dim + 1 if k.KIND == GPR_PER else dim + 1
 
 
 def dim_hp(cov: AbstractKernel, dim: int) -> int:
     """src/covariance.jl:27,60; src/compose_covar.jl:26-28."""
-    return sum(dim + 1 if is_stationary(k) else 1 for k in cov.parts())
+    return sum(part_dim_hp(k, dim) for k in cov.parts())
 
 
 def find_idx(cov: AbstractKernel, i: int, dim: int) -> Tuple[int, int, int]:
     """find_idx (src/compose_covar.jl:109-115): the part that owns the 1-based hyperparameter
     index i, as (part index, 1-based index inside the part, 0-based offset of the part's first
-    hyperparameter).  A stationary part owns dim + 1 entries, WhiteNoise one."""
+    hyperparameter).  A part owns part_dim_hp entries."""
     off = 0
     for p, k in enumerate(cov.parts()):
-        w = dim + 1 if is_stationary(k) else 1
+        w = part_dim_hp(k, dim)
         if off < i <= off + w:
             return p, i - off, off
         off += w
@@ -743,7 +768,7 @@ def _part_hps(cov: AbstractKernel, hp, dim: int):
     hp = np.asarray(hp, dtype=np.float64)
     out, off = [], 0
     for k in cov.parts():
-        w = dim + 1 if is_stationary(k) else 1
+        w = part_dim_hp(k, dim)
         out.append(hp[off:off + w])
         off += w
     return out

@@ -12,9 +12,10 @@
  * Conventions (all of them Julia's, so a Julia caller passes its arrays unchanged):
  *   - fp64 everywhere; matrices are COLUMN-MAJOR with an explicit leading dimension.
  *   - x is d x n column-major (each sample's d features contiguous), like md.x.
- *   - A kernel is described by `kinds[nk]` (GPR_SE / GPR_M32 / GPR_M52 / GPR_WN, in `+` order)
+ *   - A kernel is described by `kinds[nk]` (GPR_SE / GPR_M32 / GPR_M52 / GPR_PER / GPR_WN, in `+` order)
  *     and the flat hyper-parameter vector `hp` (HOST pointer) of length sum(dim_hp) -- SE, M32,
- *     M52: d+1 ([sigma, l_1..l_d]), WN: 1 ([sigma_n]) -- exactly split(hp, dims)
+ *     M52: d+1 ([sigma, l_1..l_d]), PER: 2d+1 ([sigma, l_1..l_d, p_1..p_d]), WN: 1 ([sigma_n])
+ *     -- exactly split(hp, dims)
  *     (src/compose_covar.jl:21-28).
  *   - Pointers named d* are DEVICE pointers (from gpr_malloc, hipMalloc, or a torch
  *     tensor); all other pointers are host pointers.  No pointer is retained after a call
@@ -41,6 +42,7 @@ extern "C" {
 #define GPR_WN 2 /* WhiteNoise  src/covariance.jl:17 */
 #define GPR_M32 3 /* Matern-3/2 (no counterpart in the reference: defined below) */
 #define GPR_M52 4 /* Matern-5/2 */
+#define GPR_PER 5 /* Periodic (no counterpart in the reference: defined below) */
 
 #define GPR_OK 0
 #define GPR_E_ARG (-1)      /* bad argument (message names it)                      */
@@ -49,7 +51,7 @@ extern "C" {
 #define GPR_E_UNSUP (-4)    /* unsupported configuration (e.g. an eigen-reduction size) */
 
 /* Kernel descriptions (kinds, nk, hp, d): any input dimension d >= 1 and any number of parts,
- * in any order, with at least one stationary part (GPR_SE, GPR_M32, GPR_M52).  For SquaredExp /
+ * in any order, with at least one stationary part (GPR_SE, GPR_M32, GPR_M52, GPR_PER).  For SquaredExp /
  * WhiteNoise parts this is the reference's envelope (src/covariance.jl:85-95,
  * src/compose_covar.jl:9-28,47-61).
  *
@@ -69,8 +71,23 @@ extern "C" {
  * stationary part on a same-object diagonal, the noise of the first WhiteNoise, the diagonal-
  * variance prior sum over ALL parts of hp_part[1]^2, LogScale when a stationary part is present.
  *
+ * GPR_PER, hp of the part [sigma, l_1..l_d, p_1..p_d] (2d + 1 values):
+ *   D = sum_k (2 l_k sin(pi (x_k - x'_k) / p_k))^2,   k = sigma^2 exp(-D)
+ * MacKay's periodic kernel as a product over dimensions, textbook length-scale 1 / (sqrt(2) l_k);
+ * the l_k are multipliers as for SquaredExp, k is even in every p_k.  A period that is zero, NaN
+ * or infinite returns GPR_E_ARG (the message names the part and the dimension; nothing is
+ * computed or written).  It is evaluated as SquaredExp on the 2d embedded features
+ * [l_k cos(2 pi x_k / p_k) | l_k sin(2 pi x_k / p_k)] (2 l sin(pi r / p) is the chord between two
+ * such points), so a description with a Periodic part takes the K-assembly paths of feature
+ * width 2d.  Derivatives, with r_k = x_k - x'_k on raw x:
+ *   dK/dsigma = (2 / |sigma|) K_p   (K_p with eps on a same-object diagonal, as for SE)
+ *   dK/dl_k   = -2 l_k K (2 sin(pi r_k / p_k))^2          (eps meets r = 0 only)
+ *   dK/dp_k   = (4 pi l_k^2 / p_k^2) K r_k sin(2 pi r_k / p_k)
+ * Every per-stationary-part rule above holds for a Periodic part unchanged (LogScale's G .*= hp
+ * covers the p entries).
+ *
  * Calls built on SquaredExp's separability or its closed-form erf integrals refuse a description
- * with a Matern part -- GPR_E_UNSUP, the message names the part, nothing is computed or written:
+ * with a Matern or Periodic part -- GPR_E_UNSUP, the message names the part, nothing is computed or written:
  * gpr_split_predict, gpr_split_predict_rows, gpr_split_predict_shard, gpr_split_predict_mgpu,
  * gpr_split_factors, gpr_integrate, gpr_integrate_noise.  (gpr_antideriv_se takes no kinds: it
  * is SquaredExp's integral of whatever hp it is given.) */
