@@ -1,17 +1,30 @@
-// Kernel-matrix assembly on gfx950: SquaredExp / composed K, cross K, dK/dtheta.
+// Kernel-matrix assembly on gfx950: SquaredExp / Matern / Periodic / composed K, cross K,
+// dK/dtheta.
 //
 // Reference: kernel_impl!(::SquaredExp) src/covariance.jl:85-95 (scale x by l, squared
 // Euclidean distance src/covariance.jl:72-77, sigma^2 exp(-D)), the +eps jitter rule
 // src/covariance.jl:49-58, the composed sum/noise src/compose_covar.jl:47-77 and the GPU
 // broadcast seam src/covar_gpu.jl:1-18 this replaces.
 //
-// Design (HBM-write bound): the inputs are pre-scaled once per SE part (xs = x .* l, the
-// reference's own rounding order) into a tiny workspace; a 64x64 output tile per 256-thread
-// workgroup keeps the row point's d features in registers and reads the column point's
-// features with scalar (wave-uniform) loads.  For the symmetric K only upper tiles are
-// computed; each is stored directly and, transposed through LDS, as its mirror tile, so
-// every N^2 element is written exactly once with 512-B coalesced column segments and the
-// exp work is halved.
+// The inputs are pre-scaled once per stationary part (xs = x .* l, the reference's own rounding
+// order; a description with a Periodic part embeds every point 2d wide) into a workspace.  K is
+// HBM-write bound and built in 64 x 64 tiles; the tile kernels of a symmetric K compute the upper
+// tiles only and store each tile and its transpose.  Four families of kernels, chosen in
+// launch_kernel_matrix / launch_kernel_matrix_for_factor:
+//  1. Upper-only strips (kmat_symu_kernel): one wave per 32-column strip segment, stores in the
+//     MFMA layout without LDS.  One or two SquaredExp parts, d <= 20, Gram form on: the whole
+//     symmetric K of a one-part description (both halves computed) and the fit's K (upper
+//     triangle + diagonal blocks; the tile-DAG mirrors the rest).
+//  2. Gram tiles (kmat_symg_kernel / kmat_crossg_kernel): the distance as an FP64 MFMA product of
+//     operands prepared once per call; k-steps compiled in up to d = 20, walked at run time above
+//     (and for part groups beyond the first KMAXP, which accumulate into K).  Every other K with
+//     the Gram form on (GPR_KBUILD_EXACT = 0, d <= GPR_KBUILD_GRAM_MAXD), a 16-B aligned K and
+//     an even ldk.
+//  3. Difference form with 16-B stores (kmat_sym2_kernel / kmat_cross2_kernel): sum_k (xa_k -
+//     xb_k)^2 on the VALU, d compiled in (1..8, 16), table exponential, at most KMAXP parts.
+//     Taken where the Gram tiles are not, with the same alignment.
+//  4. 8-byte-store fallback (kmat_cols_kernel): the difference form with the library
+//     exponential for any d, any K pointer and ldk, any number of parts -- whatever is left.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -24,11 +37,10 @@ namespace {
 
 constexpr int KT = 64;  // output tile edge
 
-// 16-B stores need a 16-B aligned K and an even leading dimension (GPR_KBUILD_SCALAR forces
-// the 8-B-store kernels, for A/B runs)
 // persistent grid of the 16-B-store kernels: 8 workgroups per CU x 256 CUs
 inline long long kbuild_grid() { return 256LL * 8; }
 
+// 16-B stores need a 16-B aligned K and an even leading dimension
 inline bool vec_store_ok(const double* K, int ldk) {
   return ((uintptr_t)K & 15) == 0 && (ldk & 1) == 0;
 }
@@ -131,17 +143,29 @@ __device__ __forceinline__ double sqdist(const double* xr, const double* __restr
   return s;
 }
 
-// Symmetric K (same-object call): upper tiles (bi <= bj) + LDS-transposed mirror.
-template <int D, bool MIX>
-__global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double* __restrict__ xs,
-                                                       int n, double* __restrict__ K,
-                                                       size_t ldk) {
-  __shared__ double tr[KT * (KT + 1)];
-  const int bid = blockIdx.x;
-  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
-  while (bj * (bj + 1) / 2 > bid) --bj;
-  const int bi = bid - bj * (bj + 1) / 2;
+// ---- 8-byte-store fallback (any d, any K pointer and ldk, any number of parts) -----------
+// One 64 x 64 tile per workgroup: lane = row i0 + lane, wave wv owns columns j0 + wv + 4c, c < 16
+// (wave-uniform: scalar loads of the column point); every store is a 512-B column segment.
+// SYM: the symmetric K of a same-object call (xps / mp unused) -- upper tiles (bi <= bj), eps per
+// part and sigma_n^2 on i == j, and the LDS-transposed mirror tile.  Else the cross K[n x mp]
+// (x !== xp): rows from xs, columns from xps, no eps, no noise.
+// (One body rather than a shared device function: with the 16 sums handed to a helper by
+// reference the compiler kept them twice, 32 more VGPRs in every instantiation.)
+template <int D, bool SYM, bool MIX>
+__global__ __launch_bounds__(256) void kmat_cols_kernel(KParams kp, const double* __restrict__ xs,
+                                                        int n, const double* __restrict__ xps,
+                                                        int mp, double* __restrict__ K, size_t ldk,
+                                                        int ntile_i) {
+  __shared__ double tr[SYM ? KT * (KT + 1) : 1];
+  const double* xcs = SYM ? xs : xps;
+  const int m = SYM ? n : mp;
+  int bi, bj;
+  if (SYM) {
+    tri_tile<false>(blockIdx.x, &bi, &bj);
+  } else {
+    bi = blockIdx.x % ntile_i;
+    bj = blockIdx.x / ntile_i;
+  }
   const int i0 = bi * KT, j0 = bj * KT;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -166,8 +190,8 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int j = j0 + wv + 4 * c;  // wave-uniform column
-      if (j < n) {
-        const double* xc = xs + ((size_t)p * n + j) * d;
+      if (j < m) {
+        const double* xc = xcs + ((size_t)p * m + j) * d;
         double dist;
         if constexpr (D > 0) {
           dist = sqdist<D>(xr, xc, d);
@@ -175,12 +199,12 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
           dist = sqdist<0>(xrow, xc, d);
         }
         double t = MIX ? kprof_neg(prof, s2, dist) : s2 * kexp_neg(dist);
-        if (i == j) t += kp.eps;
+        if (SYM && i == j) t += kp.eps;
         vals[c] = (p == 0) ? t : vals[c] + t;
       }
     }
   }
-  if (kp.has_noise) {
+  if (SYM && kp.has_noise) {
 #pragma unroll
     for (int c = 0; c < 16; ++c)
       if (i == j0 + wv + 4 * c) vals[c] += kp.noise2;
@@ -189,9 +213,9 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     const int j = j0 + wv + 4 * c;
-    if (irow && j < n) K[(size_t)i + (size_t)j * ldk] = vals[c];
+    if (irow && j < m) K[(size_t)i + (size_t)j * ldk] = vals[c];
   }
-  if (bi == bj) return;
+  if (!SYM || bi == bj) return;
   // mirror tile through LDS: tr[jl][il]
 #pragma unroll
   for (int c = 0; c < 16; ++c) tr[(wv + 4 * c) * (KT + 1) + lane] = vals[c];
@@ -202,55 +226,6 @@ __global__ __launch_bounds__(256) void kmat_sym_kernel(KParams kp, const double*
     const int jj = j0 + lane;      // mirrored row index
     const int ii = i0 + il;        // mirrored column index
     if (jj < n && ii < n) K[(size_t)jj + (size_t)ii * ldk] = tr[lane * (KT + 1) + il];
-  }
-}
-
-// Cross kernel K[n x m] (x !== xp): no eps, no noise.  Rows from xs (n), cols from xps (m).
-template <int D, bool MIX>
-__global__ __launch_bounds__(256) void kmat_cross_kernel(KParams kp, const double* __restrict__ xs,
-                                                         int n, const double* __restrict__ xps,
-                                                         int m, double* __restrict__ K,
-                                                         size_t ldk, int ntile_i) {
-  const int bi = blockIdx.x % ntile_i;
-  const int bj = blockIdx.x / ntile_i;
-  const int i0 = bi * KT, j0 = bj * KT;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int d = kp.d;
-  const int i = i0 + lane;
-  const bool irow = i < n;
-  double vals[16];
-#pragma unroll
-  for (int c = 0; c < 16; ++c) vals[c] = 0.0;
-  for (int p = 0; p < kp.nse; ++p) {
-    const double* xrow = xs + ((size_t)p * n + (irow ? i : 0)) * d;
-    double xr[D > 0 ? D : 1];
-    if constexpr (D > 0) {
-#pragma unroll
-      for (int k = 0; k < D; ++k) xr[k] = xrow[k];
-    }
-    const double s2 = kp.sig[p] * kp.sig[p];  // (any number of parts: the device table)
-    const int prof = MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-      const int j = j0 + wv + 4 * c;
-      if (j < m) {
-        const double* xc = xps + ((size_t)p * m + j) * d;
-        double dist;
-        if constexpr (D > 0) {
-          dist = sqdist<D>(xr, xc, d);
-        } else {
-          dist = sqdist<0>(xrow, xc, d);
-        }
-        const double t = MIX ? kprof_neg(prof, s2, dist) : s2 * kexp_neg(dist);
-        vals[c] = (p == 0) ? t : vals[c] + t;
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 16; ++c) {
-    const int j = j0 + wv + 4 * c;
-    if (irow && j < m) K[(size_t)i + (size_t)j * ldk] = vals[c];
   }
 }
 
@@ -313,11 +288,8 @@ __global__ void diag_scaled_identity_kernel(double* __restrict__ A, int n, size_
 __global__ __launch_bounds__(256) void mirror_upper_kernel(double* __restrict__ A, int n,
                                                            size_t lda) {
   __shared__ double tr[KT * (KT + 1)];
-  const int bid = blockIdx.x;
-  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
-  while (bj * (bj + 1) / 2 > bid) --bj;
-  const int bi = bid - bj * (bj + 1) / 2;  // bi <= bj: source tile (rows bi, cols bj)
+  int bi, bj;  // bi <= bj: source tile (rows bi, cols bj)
+  tri_tile<false>(blockIdx.x, &bi, &bj);
   const int i0 = bi * KT, j0 = bj * KT;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int c = 0; c < 16; ++c) {
@@ -472,6 +444,10 @@ __device__ __forceinline__ void store_pair(double* K, size_t idx, bool ok0, bool
   }
 }
 
+// (The two kernels below keep their tile stores written out.  They sit at the 128-VGPR limit of
+// their launch bounds, and their allocation follows the source closely: the direct store moved
+// into a helper shared with the Gram tile kernels changed spills in ten instantiations, by up
+// to 29 VGPRs where the helper took the register tile through a lambda.)
 template <int D, bool MIX>
 __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams kp, const double* __restrict__ xs,
                                                         int n, double* __restrict__ K, size_t ldk,
@@ -485,10 +461,8 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams
   // persistent: a workgroup walks tiles, so one tile's math overlaps the previous tile's
   // stores draining to HBM
   for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-    int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-    while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
-    while (bj * (bj + 1) / 2 > bid) --bj;
-    const int bi = bid - bj * (bj + 1) / 2;
+    int bi, bj;
+    tri_tile<false>(bid, &bi, &bj);
     const int i0 = bi * KT, j0 = bj * KT;
     double v[8][2];
     if (bi == bj)
@@ -547,25 +521,25 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_cross2_kernel(KPara
   }
 }
 
+// D > 0, a 16-B aligned K with an even ldk and at most KMAXP parts (the LDS tables' size): the
+// 16-B-store kernels; else the 8-byte-store fallback
 template <int D>
 void launch_sym(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, double* K, int ldk) {
   const int nt = (n + KT - 1) / KT;
   const long long nblk = (long long)nt * (nt + 1) / 2;
-  if constexpr (D > 0) {
-    if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {  // (their LDS tables hold KMAXP parts)
-      const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-      const size_t lds_bytes = sizeof(double) * (KT_LDS + 256 * kp.nse);
-      if (kp.mix)
-        kmat_sym2_kernel<D, true><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
-      else
-        kmat_sym2_kernel<D, false><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
-      return;
+  kmix_dispatch(kp.mix, [&](auto mix) {
+    constexpr bool MIX = decltype(mix)::value;
+    if constexpr (D > 0) {
+      if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {
+        const int grid = (int)std::min<long long>(nblk, kbuild_grid());
+        const size_t lds_bytes = sizeof(double) * (KT_LDS + 256 * kp.nse);
+        kmat_sym2_kernel<D, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
+        return;
+      }
     }
-  }
-  if (kp.mix)
-    kmat_sym_kernel<D, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, K, (size_t)ldk);
-  else
-    kmat_sym_kernel<D, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, K, (size_t)ldk);
+    kmat_cols_kernel<D, true, MIX><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, nullptr, 0, K,
+                                                                           (size_t)ldk, 0);
+  });
 }
 
 template <int D>
@@ -573,23 +547,19 @@ void launch_cross(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, cons
                   int m, double* K, int ldk) {
   const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
   const unsigned nblk = (unsigned)((long long)nti * ntj);
-  if constexpr (D > 0) {
-    if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {  // (their LDS tables hold KMAXP parts)
-      const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-      const size_t lds_bytes = sizeof(double) * (KT * D + 256 * kp.nse);
-      if (kp.mix)
-        kmat_cross2_kernel<D, true><<<grid, 256, lds_bytes, ctx->stream>>>(
+  kmix_dispatch(kp.mix, [&](auto mix) {
+    constexpr bool MIX = decltype(mix)::value;
+    if constexpr (D > 0) {
+      if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {
+        const int grid = (int)std::min<long long>(nblk, kbuild_grid());
+        const size_t lds_bytes = sizeof(double) * (KT * D + 256 * kp.nse);
+        kmat_cross2_kernel<D, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
             kp, xs, n, xps, m, K, (size_t)ldk, nti, (int)nblk);
-      else
-        kmat_cross2_kernel<D, false><<<grid, 256, lds_bytes, ctx->stream>>>(
-            kp, xs, n, xps, m, K, (size_t)ldk, nti, (int)nblk);
-      return;
+        return;
+      }
     }
-  }
-  if (kp.mix)
-    kmat_cross_kernel<D, true><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
-  else
-    kmat_cross_kernel<D, false><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
+    kmat_cols_kernel<D, false, MIX><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
+  });
 }
 
 // ---- Gram form of the distance on FP64 MFMA ---------------------------------------------
@@ -661,34 +631,60 @@ __global__ void gram_prep_kernel(const double* __restrict__ xs, int n, int d, in
   }
 }
 
-// One 64 x 64 tile of K on MFMA + VALU, SE parts summed in order.  Wave w owns the 32 x 32
-// quadrant (rows 32 (w & 1), cols 32 (w >> 1)): 2 x 2 blocks of 16 x 16; lane l / register q of
-// block (rb, cb) <-> row 16 rb + (l >> 4) + 4 q, col 16 cb + (l & 15).
-template <int S, bool DIAG, bool MIX>
-__device__ __forceinline__ void gram_tile(const KParams& kp, const double* __restrict__ gA,
+// One 64 x 64 tile of K on MFMA + VALU: v += the parts' terms, summed in part order.  Wave w owns
+// the 32 x 32 quadrant (rows 32 (w & 1), cols 32 (w >> 1)): 2 x 2 blocks of 16 x 16; lane l /
+// register q of block (rb, cb) <-> row 16 rb + (l >> 4) + 4 q, col 16 cb + (l & 15).  Per part the
+// four accumulators start from -|y_a|^2 - |y_b|^2, take the S k-steps (k ascending per
+// accumulator) and go through the part's profile.  Only the k-steps differ by SC:
+//  SC > 0 (S = SC compiled in, d <= 20): all 2 x 2 x S operands in registers, each block's MFMA
+//    chain right behind its accumulator's start value;
+//  SC = 0 (any d): chunks of GR_CH = 4 k-steps (16 dimensions); a chunk's 2 x 4 row and 2 x 4
+//    column operands are 16 coalesced 512-B wave loads, the next chunk's are issued before the
+//    current chunk's MFMAs (four independent accumulators per step), and the last chunk is
+//    ragged by whole k-steps: steps past S enter as zero operands, which leave every
+//    accumulator bit for bit as it was (padding inside a step is already zero in the prepared
+//    operands).  96 operand / accumulator registers whatever d is.
+// DIAG: a diagonal tile of the symmetric K -- D = 0 exactly and eps per part on i == j,
+// sigma_n^2 after the parts.
+constexpr int GR_CH = 4;  // k-steps per chunk
+template <int SC, bool DIAG, bool MIX>
+__device__ __forceinline__ void gram_tile(const KParams& kp, int S, const double* __restrict__ gA,
                                           const double* __restrict__ gB, const double* __restrict__ nA,
                                           const double* __restrict__ nB, int nblkA, int nblkB,
                                           int i0, int j0, const double* tabs, gd4 (&v)[2][2]) {
+  constexpr int NOP = SC > 0 ? SC : GR_CH;  // k-steps of operands held per 16-block
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wr = w & 1, wc = w >> 1;
   const int ba = (i0 >> 4) + 2 * wr, bb = (j0 >> 4) + 2 * wc;  // first 16-blocks
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) v[rb][cb] = gd4{0.0, 0.0, 0.0, 0.0};
   for (int p = 0; p < kp.nse; ++p) {
     const double* Ap = gA + ((size_t)p * nblkA + ba) * S * 64 + lane;
     const double* Bp = gB + ((size_t)p * nblkB + bb) * S * 64 + lane;
     const double* nAp = nA + (size_t)p * nblkA * 16 + ba * 16 + (lane >> 4);
     const double* nBp = nB + (size_t)p * nblkB * 16 + bb * 16 + (lane & 15);
-    double a[2][S], b[2][S], nr[2][4], nc[2];
+    // operands of 16-block h, k-steps NOP ch + [0, NOP) (wave-uniform bound: zero past S)
+    auto load_ops = [&](int ch, int h, double (&a)[2][NOP], double (&b)[2][NOP]) {
+#pragma unroll
+      for (int s = 0; s < NOP; ++s) {
+        const int st = NOP * ch + s;
+        const bool in = st < S;
+        a[h][s] = in ? Ap[((size_t)h * S + st) * 64] : 0.0;
+        b[h][s] = in ? Bp[((size_t)h * S + st) * 64] : 0.0;
+      }
+    };
+    // The order of the loads and of the next two loops is deliberate, and is the
+    // order each form had as a function of its own.  With S compiled in, the operand loads of
+    // half h come before that half's norm loads, and each block's MFMAs follow its start value
+    // directly, before the next block's start value; ordered differently the symmetric kernels
+    // spill up to ten more VGPRs.  With S at run time the first chunk of both halves is loaded
+    // before any norm.
+    double a[2][NOP], b[2][NOP], nr[2][4], nc[2];
+    if constexpr (SC == 0) {
+      load_ops(0, 0, a, b);
+      load_ops(0, 1, a, b);
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        a[h][s] = Ap[(h * S + s) * 64];
-        b[h][s] = Bp[(h * S + s) * 64];
-      }
+      if constexpr (SC > 0) load_ops(0, h, a, b);
 #pragma unroll
       for (int q = 0; q < 4; ++q) nr[h][q] = nAp[16 * h + 4 * q];
       nc[h] = nBp[16 * h];
@@ -700,230 +696,37 @@ __device__ __forceinline__ void gram_tile(const KParams& kp, const double* __res
       for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[rb][cb][q] = nr[rb][q] + nc[cb];
+        if constexpr (SC > 0) {
 #pragma unroll
-        for (int s = 0; s < S; ++s)
-          acc[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][s], b[cb][s], acc[rb][cb], 0, 0, 0);
-      }
-    const double* ts = tabs + 256 * p;
-    kprof_dispatch<MIX>(MIX ? kp.prof[p] : 0, [&](auto pf) {
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          double x = acc[rb][cb][q];  // -D
-          bool on_diag = false;
-          if (DIAG) {
-            on_diag = wr == wc && rb == cb && (lane >> 4) + 4 * q == (lane & 15);
-            if (on_diag) x = 0.0;
-          }
-          double t = kprof_s2<decltype(pf)::value>(-x, ts);
-          if (DIAG && on_diag) t += kp.eps;
-          v[rb][cb][q] += t;
-          if ((q + 1) % GRAM_EXPG == 0) __builtin_amdgcn_sched_barrier(0);
+          for (int s = 0; s < SC; ++s)
+            acc[rb][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][s], b[cb][s], acc[rb][cb], 0, 0, 0);
         }
-    });
-  }
-  if (DIAG && kp.has_noise && wr == wc) {
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if ((lane >> 4) + 4 * q == (lane & 15)) v[rb][rb][q] += kp.noise2;
-  }
-}
-
-// tile -> LDS, column-major with column stride 65
-__device__ __forceinline__ void gram_to_lds(const gd4 (&v)[2][2], double* T) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r0 = 32 * (w & 1) + (lane >> 4), c0 = 32 * (w >> 1) + (lane & 15);
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) T[(c0 + 16 * cb) * (KT + 1) + r0 + 16 * rb + 4 * q] = v[rb][cb][q];
-}
-
-// upper-triangle tile bid -> (bi <= bj), column-by-column order; wave-uniform
-__device__ __forceinline__ void tri_tile(int bid, int* bi, int* bj) {
-  int j = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-  while ((j + 1) * (j + 2) / 2 <= bid) ++j;
-  while (j * (j + 1) / 2 > bid) --j;
-  j = __builtin_amdgcn_readfirstlane(j);
-  *bj = j;
-  *bi = __builtin_amdgcn_readfirstlane(bid - j * (j + 1) / 2);
-}
-
-template <int S, bool MIX>
-__global__ __launch_bounds__(256, MIX ? 3 : 4) void kmat_symg_kernel(KParams kp, const double* __restrict__ gA,
-                                                         const double* __restrict__ gB,
-                                                         const double* __restrict__ nrm, int nblk,
-                                                         int n, double* __restrict__ K, size_t ldk,
-                                                         int ntiles) {
-  extern __shared__ double dyn_lds[];  // KT_LDS doubles (tile), then nse exp tables
-  double* T = dyn_lds;
-  double* tabs = dyn_lds + KT_LDS;
-  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
-  load_part_tables(kp, tabs);
-  __syncthreads();
-  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-    int bi, bj;
-    tri_tile(bid, &bi, &bj);
-    const int i0 = bi * KT, j0 = bj * KT;
-    gd4 v[2][2];
-    if (bi == bj)
-      gram_tile<S, true, MIX>(kp, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
-    else
-      gram_tile<S, false, MIX>(kp, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
-    __syncthreads();  // previous tile's LDS reads are done
-    gram_to_lds(v, T);
-    __syncthreads();
-    // direct: K[i0 + 2 l32 + {0,1}, j0 + jl] = T[jl][2 l32 + {0,1}]
-    const int i = i0 + 2 * l32;
-    if (bi == bj) {
-      // diagonal tile: the strictly-lower half mirrors the upper, so K == K^T bitwise
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const int jl = cg + 8 * c, j = j0 + jl, r0 = 2 * l32, r1 = 2 * l32 + 1;
-        const double e0 = r0 <= jl ? T[jl * (KT + 1) + r0] : T[r0 * (KT + 1) + jl];
-        const double e1 = r1 <= jl ? T[jl * (KT + 1) + r1] : T[r1 * (KT + 1) + jl];
-        if (j < n) store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, e0, e1);
       }
-      continue;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int jl = cg + 8 * c, j = j0 + jl;
-      if (j < n)
-        store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, T[jl * (KT + 1) + 2 * l32],
-                   T[jl * (KT + 1) + 2 * l32 + 1]);
-    }
-    // mirror: K[j0 + 2 l32 + {0,1}, i0 + il] = tile(il, 2 l32 + {0,1}) = T[2 l32 + {0,1}][il]
-    const int jj = j0 + 2 * l32;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int il = cg + 8 * c;
-      if (i0 + il < n)
-        store_pair(K, (size_t)jj + (size_t)(i0 + il) * ldk, jj < n, jj + 1 < n,
-                   T[(2 * l32) * (KT + 1) + il], T[(2 * l32 + 1) * (KT + 1) + il]);
-    }
-  }
-}
-
-template <int S, bool MIX>
-__global__ __launch_bounds__(256, MIX ? 3 : 4) void kmat_crossg_kernel(KParams kp, const double* __restrict__ gA,
-                                                           const double* __restrict__ gB,
-                                                           const double* __restrict__ nrmA,
-                                                           const double* __restrict__ nrmB,
-                                                           int nblkA, int nblkB, int n, int m,
-                                                           double* __restrict__ K, size_t ldk,
-                                                           int ntile_i, int ntiles) {
-  extern __shared__ double dyn_lds[];
-  double* T = dyn_lds;
-  double* tabs = dyn_lds + KT_LDS;
-  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
-  load_part_tables(kp, tabs);
-  __syncthreads();
-  for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-    const int bi = __builtin_amdgcn_readfirstlane(bid % ntile_i);
-    const int bj = __builtin_amdgcn_readfirstlane(bid / ntile_i);
-    const int i0 = bi * KT, j0 = bj * KT;
-    gd4 v[2][2];
-    gram_tile<S, false, MIX>(kp, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
-    __syncthreads();
-    gram_to_lds(v, T);
-    __syncthreads();
-    const int i = i0 + 2 * l32;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int jl = cg + 8 * c, j = j0 + jl;
-      if (j < m)
-        store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, T[jl * (KT + 1) + 2 * l32],
-                   T[jl * (KT + 1) + 2 * l32 + 1]);
-    }
-  }
-}
-
-// ---- the Gram form for any d: run-time S = ceil(d/4) -------------------------------------
-// gram_tile<S> holds all 2 x 2 x S operand registers of a wave's quadrant, so S is compiled in
-// (d <= 20).  Here the k-steps are walked in chunks of GR_CH = 4 (16 dimensions): a chunk's
-// 2 x 4 row and 2 x 4 column operands are 16 coalesced 512-B wave loads, the next chunk's are
-// issued before the current chunk's MFMA chain (four independent 16 x 16 accumulators, started
-// from -|y_a|^2 - |y_b|^2 as in gram_tile), and the last chunk is ragged by whole k-steps:
-// steps past S enter as zero operands, which leave every accumulator bit for bit as it was
-// (padding inside a step is already zero in the prepared operands).  The exponential, the
-// diagonal rule (D = 0 exactly, eps per part), the part sum and the tile stores are those of
-// kmat_symg_kernel / kmat_crossg_kernel.  96 operand/accumulator registers whatever d is.
-// ACC: the launch ADDS its parts to the K already stored (part groups beyond the first KMAXP,
-// launch_gram_groups): the tile's current values are read through LDS (coalesced 16-B loads,
-// the store pattern backwards) into the MFMA layout, then each part's term is added in part
-// order, so the element sum stays ((p1 + p2) + p3) + ... across launches.
-constexpr int GR_CH = 4;  // k-steps per chunk
-
-template <bool DIAG, bool MIX>
-__device__ __forceinline__ void gram_tile_rt(const KParams& kp, int S, const double* __restrict__ gA,
-                                             const double* __restrict__ gB,
-                                             const double* __restrict__ nA,
-                                             const double* __restrict__ nB, int nblkA, int nblkB,
-                                             int i0, int j0, const double* tabs, gd4 (&v)[2][2]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wr = w & 1, wc = w >> 1;
-  const int ba = (i0 >> 4) + 2 * wr, bb = (j0 >> 4) + 2 * wc;  // first 16-blocks
-  const int nch = (S + GR_CH - 1) / GR_CH;
-  for (int p = 0; p < kp.nse; ++p) {
-    const double* Ap = gA + ((size_t)p * nblkA + ba) * S * 64 + lane;
-    const double* Bp = gB + ((size_t)p * nblkB + bb) * S * 64 + lane;
-    const double* nAp = nA + (size_t)p * nblkA * 16 + ba * 16 + (lane >> 4);
-    const double* nBp = nB + (size_t)p * nblkB * 16 + bb * 16 + (lane & 15);
-    // operand of 16-block h, k-step s (wave-uniform bound: zero past S)
-    auto load_chunk = [&](int ch, double (&a)[2][GR_CH], double (&b)[2][GR_CH]) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int s = 0; s < GR_CH; ++s) {
-          const int st = GR_CH * ch + s;
-          const bool in = st < S;
-          a[h][s] = in ? Ap[((size_t)h * S + st) * 64] : 0.0;
-          b[h][s] = in ? Bp[((size_t)h * S + st) * 64] : 0.0;
+    if constexpr (SC == 0) {
+      const int nch = (S + GR_CH - 1) / GR_CH;
+      for (int ch = 0; ch < nch; ++ch) {
+        double an[2][GR_CH], bn[2][GR_CH];
+        if (ch + 1 < nch) {  // in flight behind this chunk's MFMAs
+          load_ops(ch + 1, 0, an, bn);
+          load_ops(ch + 1, 1, an, bn);
         }
-    };
-    double a[2][GR_CH], b[2][GR_CH];
-    load_chunk(0, a, b);
-    double nr[2][4], nc[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+        for (int s = 0; s < GR_CH; ++s)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) nr[h][q] = nAp[16 * h + 4 * q];
-      nc[h] = nBp[16 * h];
-    }
-    gd4 acc[2][2];
+          for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
+            for (int cb = 0; cb < 2; ++cb)
+              acc[rb][cb] =
+                  __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][s], b[cb][s], acc[rb][cb], 0, 0, 0);
+        if (ch + 1 < nch) {
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
+          for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[rb][cb][q] = nr[rb][q] + nc[cb];
-    for (int ch = 0; ch < nch; ++ch) {
-      double an[2][GR_CH], bn[2][GR_CH];
-      if (ch + 1 < nch) load_chunk(ch + 1, an, bn);  // in flight behind this chunk's MFMAs
-#pragma unroll
-      for (int s = 0; s < GR_CH; ++s)
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-            acc[rb][cb] =
-                __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][s], b[cb][s], acc[rb][cb], 0, 0, 0);
-      if (ch + 1 < nch) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int s = 0; s < GR_CH; ++s) {
-            a[h][s] = an[h][s];
-            b[h][s] = bn[h][s];
-          }
+            for (int s = 0; s < GR_CH; ++s) {
+              a[h][s] = an[h][s];
+              b[h][s] = bn[h][s];
+            }
+        }
       }
     }
     const double* ts = tabs + 256 * p;
@@ -956,7 +759,11 @@ __device__ __forceinline__ void gram_tile_rt(const KParams& kp, int S, const dou
   }
 }
 
-// v <- 0, or (ACC) the tile of K at (i0, j0) (rows < nr, columns < nc; 0 outside) through T
+// v <- 0, or (ACC) the tile of K at (i0, j0) (rows < nr, columns < nc; 0 outside): the launch
+// ADDS its parts to the K already stored (part groups beyond the first KMAXP, launch_gram_groups).
+// The tile's current values are read through T (coalesced 16-B loads, the store pattern
+// backwards) into the MFMA layout; each part's term is then added in part order, so the element
+// sum stays ((p1 + p2) + p3) + ... across launches.
 template <bool ACC>
 __device__ __forceinline__ void gram_tile_init(const double* __restrict__ K, size_t ldk, int i0,
                                                int j0, int nr, int nc, double* T,
@@ -999,17 +806,73 @@ __device__ __forceinline__ void gram_tile_init(const double* __restrict__ K, siz
       for (int q = 0; q < 4; ++q) v[rb][cb][q] = T[(c0 + 16 * cb) * (KT + 1) + r0 + 16 * rb + 4 * q];
 }
 
-template <bool ACC, bool MIX>
-__global__ __launch_bounds__(256, 2) void kmat_symgr_kernel(KParams kp, int S,
-                                                            const double* __restrict__ gA,
-                                                            const double* __restrict__ gB,
-                                                            const double* __restrict__ nrm,
-                                                            int nblk, int n, double* __restrict__ K,
-                                                            size_t ldk, int ntiles) {
+// tile -> LDS, column-major with column stride 65
+__device__ __forceinline__ void gram_to_lds(const gd4 (&v)[2][2], double* T) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r0 = 32 * (w & 1) + (lane >> 4), c0 = 32 * (w >> 1) + (lane & 15);
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) T[(c0 + 16 * cb) * (KT + 1) + r0 + 16 * rb + 4 * q] = v[rb][cb][q];
+}
+
+// The three stores of a tile held in T (gram_to_lds: element (r, c) at T[c][r]), 16-B row pairs.
+// direct: K[i0 + 2 l32 + {0,1}, j0 + jl] = T[jl][2 l32 + {0,1}], rows < nr, columns < nc
+__device__ __forceinline__ void tile_store_direct(const double* T, double* __restrict__ K,
+                                                  size_t ldk, int i0, int j0, int nr, int nc) {
+  const int l32 = threadIdx.x & 31, cg = threadIdx.x >> 5;
+  const int i = i0 + 2 * l32;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int jl = cg + 8 * c, j = j0 + jl;
+    if (j < nc)
+      store_pair(K, (size_t)i + (size_t)j * ldk, i < nr, i + 1 < nr, T[jl * (KT + 1) + 2 * l32],
+                 T[jl * (KT + 1) + 2 * l32 + 1]);
+  }
+}
+// diagonal tile: the strictly-lower half mirrors the upper, so K == K^T bitwise
+__device__ __forceinline__ void tile_store_diag(const double* T, double* __restrict__ K, size_t ldk,
+                                                int i0, int n) {
+  const int l32 = threadIdx.x & 31, cg = threadIdx.x >> 5;
+  const int i = i0 + 2 * l32;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int jl = cg + 8 * c, j = i0 + jl, r0 = 2 * l32, r1 = 2 * l32 + 1;
+    const double e0 = r0 <= jl ? T[jl * (KT + 1) + r0] : T[r0 * (KT + 1) + jl];
+    const double e1 = r1 <= jl ? T[jl * (KT + 1) + r1] : T[r1 * (KT + 1) + jl];
+    if (j < n) store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, e0, e1);
+  }
+}
+// mirror: K[j0 + 2 l32 + {0,1}, i0 + il] = tile(il, 2 l32 + {0,1}) = T[2 l32 + {0,1}][il]
+__device__ __forceinline__ void tile_store_mirror(const double* T, double* __restrict__ K,
+                                                  size_t ldk, int i0, int j0, int n) {
+  const int l32 = threadIdx.x & 31, cg = threadIdx.x >> 5;
+  const int jj = j0 + 2 * l32;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int il = cg + 8 * c;
+    if (i0 + il < n)
+      store_pair(K, (size_t)jj + (size_t)(i0 + il) * ldk, jj < n, jj + 1 < n,
+                 T[(2 * l32) * (KT + 1) + il], T[(2 * l32 + 1) * (KT + 1) + il]);
+  }
+}
+
+// The Gram tile kernels: persistent workgroups walk 64 x 64 tiles; a tile is computed in the MFMA
+// layout, passed through T and stored as 16-B row pairs.  SC > 0: S = SC k-steps compiled in
+// (3 or 4 workgroups per CU); SC = 0: S at run time, 2 workgroups per CU, and with
+// ACC the tile adds to the K already stored.  Srt is read only by the SC = 0 instances (the others
+// take and ignore it, so that one launch line serves both).
+template <int SC, bool ACC, bool MIX>
+__global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_symg_kernel(
+    KParams kp, int Srt, const double* __restrict__ gA, const double* __restrict__ gB,
+    const double* __restrict__ nrm, int nblk, int n, double* __restrict__ K, size_t ldk,
+    int ntiles) {
   extern __shared__ double dyn_lds[];  // KT_LDS doubles (tile), then nse exp tables
   double* T = dyn_lds;
   double* tabs = dyn_lds + KT_LDS;
-  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
+  const int S = SC > 0 ? SC : Srt;
   load_part_tables(kp, tabs);
   __syncthreads();
   for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
@@ -1019,51 +882,30 @@ __global__ __launch_bounds__(256, 2) void kmat_symgr_kernel(KParams kp, int S,
     gd4 v[2][2];
     gram_tile_init<ACC>(K, ldk, i0, j0, n, n, T, v);
     if (bi == bj)
-      gram_tile_rt<true, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile<SC, true, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
     else
-      gram_tile_rt<false, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile<SC, false, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
     __syncthreads();  // previous tile's LDS reads are done
     gram_to_lds(v, T);
     __syncthreads();
-    const int i = i0 + 2 * l32;
     if (bi == bj) {
-      // diagonal tile: the strictly-lower half mirrors the upper, so K == K^T bitwise
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const int jl = cg + 8 * c, j = j0 + jl, r0 = 2 * l32, r1 = 2 * l32 + 1;
-        const double e0 = r0 <= jl ? T[jl * (KT + 1) + r0] : T[r0 * (KT + 1) + jl];
-        const double e1 = r1 <= jl ? T[jl * (KT + 1) + r1] : T[r1 * (KT + 1) + jl];
-        if (j < n) store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, e0, e1);
-      }
+      tile_store_diag(T, K, ldk, i0, n);
       continue;
     }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int jl = cg + 8 * c, j = j0 + jl;
-      if (j < n)
-        store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, T[jl * (KT + 1) + 2 * l32],
-                   T[jl * (KT + 1) + 2 * l32 + 1]);
-    }
-    const int jj = j0 + 2 * l32;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int il = cg + 8 * c;
-      if (i0 + il < n)
-        store_pair(K, (size_t)jj + (size_t)(i0 + il) * ldk, jj < n, jj + 1 < n,
-                   T[(2 * l32) * (KT + 1) + il], T[(2 * l32 + 1) * (KT + 1) + il]);
-    }
+    tile_store_direct(T, K, ldk, i0, j0, n, n);
+    tile_store_mirror(T, K, ldk, i0, j0, n);
   }
 }
 
-template <bool ACC, bool MIX>
-__global__ __launch_bounds__(256, 2) void kmat_crossgr_kernel(
-    KParams kp, int S, const double* __restrict__ gA, const double* __restrict__ gB,
+template <int SC, bool ACC, bool MIX>
+__global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_crossg_kernel(
+    KParams kp, int Srt, const double* __restrict__ gA, const double* __restrict__ gB,
     const double* __restrict__ nrmA, const double* __restrict__ nrmB, int nblkA, int nblkB, int n,
     int m, double* __restrict__ K, size_t ldk, int ntile_i, int ntiles) {
   extern __shared__ double dyn_lds[];
   double* T = dyn_lds;
   double* tabs = dyn_lds + KT_LDS;
-  const int t = threadIdx.x, l32 = t & 31, cg = t >> 5;
+  const int S = SC > 0 ? SC : Srt;
   load_part_tables(kp, tabs);
   __syncthreads();
   for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
@@ -1072,18 +914,11 @@ __global__ __launch_bounds__(256, 2) void kmat_crossgr_kernel(
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
     gram_tile_init<ACC>(K, ldk, i0, j0, n, m, T, v);
-    gram_tile_rt<false, MIX>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
+    gram_tile<SC, false, MIX>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
     __syncthreads();
     gram_to_lds(v, T);
     __syncthreads();
-    const int i = i0 + 2 * l32;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int jl = cg + 8 * c, j = j0 + jl;
-      if (j < m)
-        store_pair(K, (size_t)i + (size_t)j * ldk, i < n, i + 1 < n, T[jl * (KT + 1) + 2 * l32],
-                   T[jl * (KT + 1) + 2 * l32 + 1]);
-    }
+    tile_store_direct(T, K, ldk, i0, j0, n, m);
   }
 }
 
@@ -1358,7 +1193,7 @@ __global__ __launch_bounds__(256, KU_MINB) void kmat_symu_kernel(KParams kp, con
 // the Gram form (MFMA distance) up to d = GPR_KBUILD_GRAM_MAXD unless the context asks for the
 // reference's difference form (GPR_KBUILD_EXACT knob); GRAM_CT_MAXD: the largest d of the
 // kernels compiled per S = ceil(d/4) (gram_tile<S>, the upper-only build) -- above it the
-// run-time-S tile (gram_tile_rt)
+// run-time-S tile (gram_tile<0>)
 constexpr int GRAM_CT_MAXD = 4 * 5;
 inline bool gram_enabled(const gpr_ctx* ctx, int d) {
   return !ctx->kbuild_exact && d <= ctx->kbuild_gram_maxd;
@@ -1370,18 +1205,20 @@ inline size_t gram_centres_cap(const KParams& kp) {
   return std::max((size_t)kp.nse * kp.d, (size_t)256);
 }
 
-// S > 0: the kernels compiled for S k-steps; S = 0: the run-time-S kernels (any d), which with
-// acc add their parts to the K already stored (launch_gram_groups)
-template <int SC, bool MIX>
-int launch_gram_m(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
-                  int m, int same, double* K, int ldk, int acc) {
+// The prepared operands of one Gram build (S k-steps): the centres of the row points, the row
+// operands x 2.0 with the row norms, the column operands x 1.0 -- of the same points (same: no
+// second set of norms, everything carved from dgA) or of xps with their own norms (dgB).
+struct GramOps {
+  double *A, *nrmA, *B, *nrmB;
+  int nbA, nbB;  // 16-blocks, points padded to a multiple of KT
+};
+int gram_prepare(gpr_ctx* ctx, const KParams& kp, int S, const double* xs, int n,
+                 const double* xps, int m, int same, GramOps* o) {
   const int d = kp.d;
-  const int S = SC > 0 ? SC : (d + 3) / 4;
   const int nbA = ((n + KT - 1) / KT) * (KT / 16);
   const int nbB = same ? nbA : ((m + KT - 1) / KT) * (KT / 16);
   const size_t opA = (size_t)kp.nse * nbA * S * 64, opB = same ? 0 : (size_t)kp.nse * nbB * S * 64;
   const size_t nA = (size_t)kp.nse * nbA * 16, nB = same ? 0 : (size_t)kp.nse * nbB * 16;
-  // dgA: row operands + row norms; dgB: column operands + column norms (cross only)
   GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, gram_centres_cap(kp)));
   GPR_TRY(ensure_buf(ctx, &ctx->dgA, &ctx->gA_cap, opA + nA + (same ? opA : 0)));
   if (!same) GPR_TRY(ensure_buf(ctx, &ctx->dgB, &ctx->gB_cap, opB + nB));
@@ -1399,60 +1236,42 @@ int launch_gram_m(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, cons
   prep(xs, n, nbA, 2.0, A, nrmA);
   prep(same ? xs : xps, same ? n : m, nbB, 1.0, B, same ? nullptr : nrmB);
   LAUNCH_CHECK(ctx);
+  *o = GramOps{A, nrmA, B, nrmB, nbA, nbB};
+  return 0;
+}
+
+// SC > 0: the tile kernels compiled for SC k-steps; SC = 0: the run-time-S ones (any d), which
+// with ACC add their parts to the K already stored (launch_gram_groups).  SE-only descriptions
+// (and SE-only groups of a mixed one) launch the MIX = false instantiations; a group with another
+// profile the MIX ones (one scalar branch per part).
+template <int SC, bool ACC = false>
+int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
+                int m, int same, double* K, int ldk) {
+  static_assert(SC == 0 || !ACC, "only the run-time-S kernels accumulate");
+  const int S = SC > 0 ? SC : (kp.d + 3) / 4;
+  GramOps g;
+  GPR_TRY(gram_prepare(ctx, kp, S, xs, n, xps, m, same, &g));
   const size_t lds_bytes = sizeof(double) * (KT_LDS + 256 * kp.nse);
-  if (same) {
-    const int nt = (n + KT - 1) / KT;
-    const long long nblk = (long long)nt * (nt + 1) / 2;
-    const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-    if constexpr (SC > 0)
-      kmat_symg_kernel<SC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, A, B, nrmA, nbA, n, K,
-                                                                  (size_t)ldk, (int)nblk);
-    else if (acc)
-      kmat_symgr_kernel<true, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
-                                                                     (size_t)ldk, (int)nblk);
+  const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
+  const long long nblk = same ? (long long)nti * (nti + 1) / 2 : (long long)nti * ntj;
+  const int grid = (int)std::min<long long>(nblk, kbuild_grid());
+  kmix_dispatch(kp.mix, [&](auto mix) {
+    constexpr bool MIX = decltype(mix)::value;
+    if (same)
+      kmat_symg_kernel<SC, ACC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
+          kp, S, g.A, g.B, g.nrmA, g.nbA, n, K, (size_t)ldk, (int)nblk);
     else
-      kmat_symgr_kernel<false, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, S, A, B, nrmA, nbA, n, K,
-                                                                      (size_t)ldk, (int)nblk);
-  } else {
-    const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
-    const long long nblk = (long long)nti * ntj;
-    const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-    if constexpr (SC > 0)
-      kmat_crossg_kernel<SC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
-          kp, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
-    else if (acc)
-      kmat_crossgr_kernel<true, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
-          kp, S, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
-    else
-      kmat_crossgr_kernel<false, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
-          kp, S, A, B, nrmA, nrmB, nbA, nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
-  }
+      kmat_crossg_kernel<SC, ACC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
+          kp, S, g.A, g.B, g.nrmA, g.nrmB, g.nbA, g.nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
+  });
   LAUNCH_CHECK(ctx);
   return 0;
 }
 
-// SE-only descriptions (and SE-only groups of a mixed one) launch the instantiations they
-// always launched; a group with a Matern part the MIX ones (one scalar branch per part)
-template <int SC>
-int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
-                int m, int same, double* K, int ldk, int acc = 0) {
-  return kp.mix ? launch_gram_m<SC, true>(ctx, kp, xs, n, xps, m, same, K, ldk, acc)
-                : launch_gram_m<SC, false>(ctx, kp, xs, n, xps, m, same, K, ldk, acc);
-}
-
-// the upper-only build (kmat_symu_kernel, SquaredExp parts only): operands as launch_gram's
-// same-object path
+// the upper-only build (kmat_symu_kernel, SquaredExp parts only) on the same-object operands
 template <int S, int NSE>
 int launch_gram_upper(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, double* K, int ldk,
                       int full) {
-  const int d = kp.d;
-  const int nbA = ((n + KT - 1) / KT) * (KT / 16);
-  const size_t opA = (size_t)NSE * nbA * S * 64, nA = (size_t)NSE * nbA * 16;
-  GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, gram_centres_cap(kp)));
-  GPR_TRY(ensure_buf(ctx, &ctx->dgA, &ctx->gA_cap, 2 * opA + nA));
-  double* A = ctx->dgA;
-  double* nrmA = A + opA;
-  double* B = nrmA + nA;
   // GPR_KBUILD_COLSTORE (single-part builds): interior items stored a column's 128 rows per
   // instruction through 16.6 KB of LDS per wave (16-B stores: K 16-B aligned, ldk even), and
   // one item per wave (no persistent loop: the hardware dispatches the items in list order, so
@@ -1513,18 +1332,14 @@ int launch_gram_upper(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, 
     kl->key = key;
   }
   kl->used = ++ctx->kup_clock;
-  gram_center_kernel<<<NSE * d, 256, 0, ctx->stream>>>(xs, n, d, ctx->dgc);
-  {
-    const size_t total = opA;
-    const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-    gram_prep_kernel<<<blocks, 256, 0, ctx->stream>>>(xs, n, d, S, nbA, NSE, ctx->dgc, 2.0, A, nrmA);
-    gram_prep_kernel<<<blocks, 256, 0, ctx->stream>>>(xs, n, d, S, nbA, NSE, ctx->dgc, 1.0, B, nullptr);
-  }
-  LAUNCH_CHECK(ctx);
+  if (kp.nse != NSE)  // (gram_prepare sizes and launches by kp.nse, the kernel by NSE)
+    return set_err(ctx, GPR_E_ARG, "upper-only build: %d parts, kernel compiled for %d", kp.nse, NSE);
+  GramOps g;
+  GPR_TRY(gram_prepare(ctx, kp, S, xs, n, nullptr, n, 1, &g));
   const int grid = (int)std::max(1LL, std::min((long long)(kl->nitems + 3) / 4, 256LL * wgs));
   const size_t lds = sizeof(double) * ((256 + 4 * KU_W) * NSE + (colstore ? 4 * 16 * KU_SP : 0));
   kmat_symu_kernel<S, NSE><<<grid, 256, lds, ctx->stream>>>(
-      kp, A, B, nrmA, nbA, n, K, (size_t)ldk, kl->d, kl->nitems, full, colstore);
+      kp, g.A, g.B, g.nrmA, g.nbA, n, K, (size_t)ldk, kl->d, kl->nitems, full, colstore);
   LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1566,7 +1381,7 @@ int launch_gram_groups(gpr_ctx* ctx, const KParams& kp, const double* xs, int n,
     const double* gx = xs + (size_t)p0 * n * kp.d;
     const double* gxp = same ? nullptr : xps + (size_t)p0 * m * kp.d;
     if (p0 == 0) GPR_TRY(launch_gram_any(ctx, g, gx, n, gxp, m, same, K, ldk));
-    else GPR_TRY(launch_gram<0>(ctx, g, gx, n, gxp, m, same, K, ldk, 1));
+    else GPR_TRY((launch_gram<0, true>(ctx, g, gx, n, gxp, m, same, K, ldk)));
   }
   return 0;
 }

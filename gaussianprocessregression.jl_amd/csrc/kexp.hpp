@@ -1,8 +1,12 @@
-// exp(-dist) scaled by a part's sigma^2 via an LDS table: shared by the K-assembly kernels
-// (assembly.hip) and the fused MLL gradient (mll.hip), so both evaluate the kernel with the
-// same ~1-ulp exponential.
+// What the K-assembly kernels (assembly.hip) and the fused MLL gradient (mll.hip) share:
+//  - exp(-dist) scaled by a part's sigma^2 via an LDS table, so both evaluate the kernel with
+//    the same ~1-ulp exponential, and the radial profiles built on it (kprof_*);
+//  - the per-part profile dispatch (kprof_dispatch) and its host half (kmix_dispatch);
+//  - the walk over the upper-triangle tiles (tri_tile).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #ifndef GPR_EXP32  // 1: 32-entry exp tables (conflict-free LDS gathers, 2 more FMAs)
 #define GPR_EXP32 0
@@ -142,6 +146,13 @@ static __device__ __forceinline__ void kprof_dispatch(int prof, F&& f) {
   }
 }
 
+// Host side of MIX: f(std::bool_constant<MIX>) with MIX = the description has a non-SquaredExp
+// profile (KParams::mix) -- the one place a launcher picks between a kernel's two instantiations.
+template <class F>
+static inline auto kmix_dispatch(bool mix, F&& f) {
+  return mix ? f(std::true_type{}) : f(std::false_type{});
+}
+
 // the same without the clamp (3 VALU fewer), for callers that have bounded dist < 5.8e6, so
 // that n fits the int32 low word: below -745 the ldexp underflows to 0 as in the clamped form,
 // and a NaN propagates
@@ -151,4 +162,24 @@ static __device__ __forceinline__ double kexp_s2_nc(double dist, const double* t
 #else
   return kexp_core(-dist, ts);
 #endif
+}
+
+// Upper-triangle tile bid -> (bi <= bj), column-by-column order (bid = bj (bj + 1) / 2 + bi).
+// The tile walk shared by the symmetric K kernels and the MLL gradient pass.  SCALAR: the
+// results are pinned to SGPRs (readfirstlane; bid is wave-uniform either way).  The kernels that
+// decoded the index in place before this function existed call it with SCALAR = false and keep
+// the register allocation they had: several sit at their launch bounds' VGPR limit, where the
+// pinned form moved spills (kmat_sym2_kernel<16, true>: 303 -> 307).
+template <bool SCALAR = true>
+static __device__ __forceinline__ void tri_tile(int bid, int* bi, int* bj) {
+  int j = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
+  while ((j + 1) * (j + 2) / 2 <= bid) ++j;
+  while (j * (j + 1) / 2 > bid) --j;
+  int i = bid - j * (j + 1) / 2;
+  if (SCALAR) {
+    j = __builtin_amdgcn_readfirstlane(j);
+    i = __builtin_amdgcn_readfirstlane(bid - j * (j + 1) / 2);
+  }
+  *bj = j;
+  *bi = i;
 }

@@ -52,6 +52,92 @@ __global__ __launch_bounds__(1024) void mll_terms_kernel(const double* __restric
   }
 }
 
+// ---- the pieces of the gradient kernels, written once --------------------------------------
+// (mll_grad_wide_kernel, which is the wide and the Periodic pass, uses all of them;
+// mll_grad_tiles_kernel the tile index and the reduction, see there.  grad_tile, grad_fill_tabs
+// and grad_store_wn therefore exist a second time, written out in mll_grad_tiles_kernel: a fix
+// to one of them must be made in both places.)
+// A thread's place in the pass: one workgroup per upper tile (bi <= bj), lane = row i0 + lane,
+// wave wv = the 16 columns j0 + wv + 4c.  Columns past n are clamped to point n - 1 with zero
+// weight.
+struct GradTile {
+  int bi, bj, i0, j0, lane, wv, i;
+  bool irow;    // i < n
+  size_t irc;   // the row, clamped
+  double wgt;   // off-diagonal tiles count twice (symmetry)
+  double ai;    // alpha_i (0 past n)
+  double s_wn;  // WhiteNoise term: alpha_a^2 - Kinv_aa from the thread whose columns hold a
+                // (diagonal tiles only)
+};
+__device__ __forceinline__ GradTile grad_tile(int n, const double* __restrict__ Kinv, size_t ldk,
+                                              const double* __restrict__ alpha) {
+  GradTile g;
+  tri_tile<false>(blockIdx.x, &g.bi, &g.bj);
+  g.i0 = g.bi * GT;
+  g.j0 = g.bj * GT;
+  g.lane = threadIdx.x & 63;
+  g.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  g.i = g.i0 + g.lane;
+  g.irow = g.i < n;
+  g.irc = (size_t)min(g.i, n - 1);
+  g.wgt = (g.bi == g.bj) ? 1.0 : 2.0;
+  g.ai = g.irow ? alpha[g.i] : 0.0;
+  g.s_wn = 0.0;
+  if (g.bi == g.bj && g.irow && ((g.lane - g.wv) & 3) == 0)
+    g.s_wn = g.ai * g.ai - Kinv[(size_t)g.i + (size_t)g.i * ldk];
+  return g;
+}
+
+// the exp tables sigma_p^2 2^(j/256) of the group of up to KMAXP parts that starts at part p0
+__device__ __forceinline__ void grad_fill_tabs(const KParams& kp, int p0, double (*tabs)[256]) {
+  for (int g = p0; g < min(kp.nse, p0 + KMAXP); ++g)
+    tabs[g - p0][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
+}
+
+// A part's sums to its slots: acc_s (already summed over the wave) and the N per-thread sums
+// acc[] through red[wave][1 + N] to out[dst(t)] for t in [t0, nt) (dst(t) < 0: no slot), the four
+// waves added in a fixed order.
+template <int N, int W, class Dst>
+__device__ __forceinline__ void grad_reduce(int lane, int wv, double acc_s, double (&acc)[N],
+                                            double (&red)[4][W], int t0, int nt,
+                                            double* __restrict__ out, Dst&& dst) {
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+  __syncthreads();
+  if (lane == 0) {
+    red[wv][0] = acc_s;
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[wv][1 + k] = acc[k];
+  }
+  __syncthreads();
+  for (int t = threadIdx.x + t0; t < nt; t += 256) {
+    const int s = dst(t);
+    if (s >= 0) out[s] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+  }
+}
+
+// WhiteNoise term: sum_a (alpha_a^2 - Kinv_aa) (only diagonal tiles contribute), through the
+// last column of red
+template <int W>
+__device__ __forceinline__ void grad_store_wn(const GradTile& g, double (&red)[4][W],
+                                              double* __restrict__ out) {
+  double s_wn = g.s_wn;
+  for (int o = 32; o > 0; o >>= 1) s_wn += __shfl_xor(s_wn, o);
+  __syncthreads();
+  if (g.lane == 0) red[g.wv][W - 1] = s_wn;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = red[0][W - 1] + red[1][W - 1] + red[2][W - 1] + red[3][W - 1];
+}
+
+// (This kernel shares tri_tile and grad_reduce only.  Its prologue, table fill and WhiteNoise
+// epilogue are the lines of grad_tile, grad_fill_tabs and grad_store_wn written out: taken through
+// those helpers, every instance kept its register counts within a few SGPR spills, but the
+// compiler scheduled the column loop differently, and gpr_mll_grad measured 1.1 % slower at
+// d = 32 and 0.6 % at d = 16 with a Matern part.  As it stands the column loop compiles to the
+// instructions and registers it had before the helpers existed in 18 of the 20 instances.
+// A fix to one of the three helpers must be repeated in the lines marked [grad_tile],
+// [grad_fill_tabs] and [grad_store_wn] below.)
 // partial[bid][slot]: slot layout = for each stationary part p: [S_sigma, S_l1..S_ld], then
 // S_wn.  S_sigma sums mv K_p, S_lk sums mv W_p r_k^2.  MIX: the description has a Matern part
 // (each part's profile from the device table, one scalar branch per part); SE-only
@@ -66,10 +152,9 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
   __shared__ double red[4][D + 2];
   __shared__ double tabs[KMAXP][256];  // sigma_p^2 2^(j/256)
   const int bid = blockIdx.x;
-  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
-  while (bj * (bj + 1) / 2 > bid) --bj;
-  const int bi = bid - bj * (bj + 1) / 2;
+  // [grad_tile] from here to s_wn
+  int bi, bj;
+  tri_tile<false>(bid, &bi, &bj);
   const int i0 = bi * GT, j0 = bj * GT;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -78,6 +163,7 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
   const bool irow = i < n;
   const double wgt = (bi == bj) ? 1.0 : 2.0;
   // (the tables of the first KMAXP parts; further groups of KMAXP re-fill them below)
+  // [grad_fill_tabs]
   for (int p = 0; p < min(kp.nse, KMAXP); ++p)
     tabs[p][threadIdx.x] = (kp.sig[p] * kp.sig[p]) * kp.exptab[threadIdx.x];
 
@@ -95,7 +181,7 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
   for (int p = 0; p < kp.nse; ++p) {
     if (p > 0 && (p & (KMAXP - 1)) == 0) {  // next group of parts: its exp tables
       __syncthreads();
-      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)
+      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)  // [grad_fill_tabs]
         tabs[g - p][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
       __syncthreads();
     }
@@ -150,21 +236,11 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
     });
     // workgroup reduction of (acc_s, acc_l[0..d)) -> partial slots
     for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-      for (int o = 32; o > 0; o >>= 1) acc_l[k] += __shfl_xor(acc_l[k], o);
-    __syncthreads();
-    if (lane == 0) {
-      red[wv][0] = acc_s;
-#pragma unroll
-      for (int k = 0; k < D; ++k) red[wv][1 + k] = acc_l[k];
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < d + 1; t += 256)
-      partial[(size_t)bid * nslot + slot + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+    grad_reduce(lane, wv, acc_s, acc_l, red, 0, d + 1, partial + (size_t)bid * nslot + slot,
+                [](int t) { return t; });
     slot += d + 1;
   }
-  // WhiteNoise term: sum_a (alpha_a^2 - Kinv_aa) (only diagonal tiles contribute)
+  // [grad_store_wn] WhiteNoise term: sum_a (alpha_a^2 - Kinv_aa) (only diagonal tiles contribute)
   for (int o = 32; o > 0; o >>= 1) s_wn += __shfl_xor(s_wn, o);
   __syncthreads();
   if (lane == 0) red[wv][D + 1] = s_wn;
@@ -173,8 +249,9 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
     partial[(size_t)bid * nslot + slot] = red[0][D + 1] + red[1][D + 1] + red[2][D + 1] + red[3][D + 1];
 }
 
-// The same pass for d > 32, where the row point and its d sums no longer fit in registers.  Per
-// SE part and 64 x 64 tile, two phases:
+// The same pass for any d, for d > 32 (where the row point and its d sums no longer fit in
+// registers) and for a description with a Periodic part (PER).  Per part and 64 x 64 tile, two
+// phases:
 //  1. each thread's 16 weights mk_c = w (alpha_a alpha_b - Kinv_ab) W_p,ab (K_p,ab for
 //     SquaredExp; S_sigma sums the K_p ones), the distance by a
 //     run-time loop over all d (row point from global memory / L1, column point wave-uniform);
@@ -186,126 +263,10 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
 //     mk_c (x_ka - x_kb)^2 over the 16 columns (column points re-read from L2, scalar loads),
 //     reduced as in mll_grad_tiles_kernel into slots 1 + 32 chunk + k.
 // S_sigma and the WhiteNoise slot are written once.  Same slot layout, same reduction kernel.
-constexpr int GW = 32;
-template <bool MIX>
-__global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const double* __restrict__ X,
-                                                            int n, const double* __restrict__ Kinv,
-                                                            size_t ldk, const double* __restrict__ alpha,
-                                                            double* __restrict__ partial, int nslot) {
-  __shared__ double red[4][GW + 2];
-  __shared__ double tabs[KMAXP][256];  // sigma_p^2 2^(j/256)
-  __shared__ double mks[16][256];      // mk_c of every thread
-  const int bid = blockIdx.x;
-  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
-  while (bj * (bj + 1) / 2 > bid) --bj;
-  const int bi = bid - bj * (bj + 1) / 2;
-  const int i0 = bi * GT, j0 = bj * GT;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int d = kp.d;
-  const int i = i0 + lane;
-  const bool irow = i < n;
-  const double wgt = (bi == bj) ? 1.0 : 2.0;
-  const size_t irc = (size_t)min(i, n - 1);
-  const double* xrow = X + irc * d;
-
-  const double ai = irow ? alpha[i] : 0.0;
-  double s_wn = 0.0;
-  if (bi == bj && irow && ((lane - wv) & 3) == 0) s_wn = ai * ai - Kinv[(size_t)i + (size_t)i * ldk];
-
-  int slot = 0;
-  for (int p = 0; p < kp.nse; ++p) {
-    if ((p & (KMAXP - 1)) == 0) {  // this group of parts' exp tables
-      __syncthreads();
-      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)
-        tabs[g - p][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
-      __syncthreads();
-    }
-    const double* ts = tabs[p & (KMAXP - 1)];
-    const double* l2p = kp.l2 + (size_t)p * d;
-    // phase 1: the 16 weights
-    double acc_s = 0.0;
-    kprof_dispatch<MIX>(MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0, [&](auto pf) {
-#pragma unroll 1
-    for (int c = 0; c < 16; ++c) {
-      const int jr = j0 + wv + 4 * c;
-      const int j = min(jr, n - 1);  // wave-uniform: scalar loads of the point
-      const double kin = Kinv[irc + (size_t)j * ldk];
-      const double mv = (irow && jr < n) ? wgt * (ai * alpha[j] - kin) : 0.0;
-      const double* xc = X + (size_t)j * d;
-      double dpart[4] = {0.0, 0.0, 0.0, 0.0};
-      int k = 0;
-#pragma unroll 1
-      for (; k + 4 <= d; k += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const double r = xrow[k + u] - xc[k + u];
-          dpart[u] = fma(l2p[k + u], r * r, dpart[u]);
-        }
-      }
-      for (; k < d; ++k) {
-        const double r = xrow[k] - xc[k];
-        dpart[k & 3] = fma(l2p[k], r * r, dpart[k & 3]);
-      }
-      const double dist = (dpart[0] + dpart[1]) + (dpart[2] + dpart[3]);
-      double Wp;
-      const double Kp = kprof_s2_w<decltype(pf)::value>(dist, ts, &Wp) + (i == j ? kp.eps : 0.0);
-      const double mk = mv * Kp;
-      mks[c][threadIdx.x] = decltype(pf)::value == 0 ? mk : mv * Wp;  // phase 2's weight
-      acc_s += mk;
-    }
-    });
-    for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
-    // phase 2: the length-scale sums, GW dimensions at a time
-    for (int k0 = 0; k0 < d; k0 += GW) {
-      const int kn = min(GW, d - k0);  // wave-uniform
-      double xr[GW], acc_l[GW];
-#pragma unroll
-      for (int k = 0; k < GW; ++k) {
-        xr[k] = k < kn ? xrow[k0 + k] : 0.0;
-        acc_l[k] = 0.0;
-      }
-#pragma unroll 1
-      for (int c = 0; c < 16; ++c) {
-        const int j = min(j0 + wv + 4 * c, n - 1);
-        const double* xc = X + (size_t)j * d + k0;
-        const double mk = mks[c][threadIdx.x];
-#pragma unroll
-        for (int k = 0; k < GW; ++k) {
-          const double r = xr[k] - (k < kn ? xc[k] : 0.0);
-          acc_l[k] = fma(mk, r * r, acc_l[k]);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < GW; ++k)
-        for (int o = 32; o > 0; o >>= 1) acc_l[k] += __shfl_xor(acc_l[k], o);
-      __syncthreads();
-      if (lane == 0) {
-        red[wv][0] = acc_s;
-#pragma unroll
-        for (int k = 0; k < GW; ++k) red[wv][1 + k] = acc_l[k];
-      }
-      __syncthreads();
-      // slot 0 of the part (S_sigma) with the first chunk, then this chunk's kn sums
-      for (int t = threadIdx.x + (k0 ? 1 : 0); t < kn + 1; t += 256)
-        partial[(size_t)bid * nslot + slot + (t ? k0 + t : 0)] =
-            red[0][t] + red[1][t] + red[2][t] + red[3][t];
-    }
-    slot += d + 1;
-  }
-  for (int o = 32; o > 0; o >>= 1) s_wn += __shfl_xor(s_wn, o);
-  __syncthreads();
-  if (lane == 0) red[wv][GW + 1] = s_wn;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    partial[(size_t)bid * nslot + slot] = red[0][GW + 1] + red[1][GW + 1] + red[2][GW + 1] + red[3][GW + 1];
-}
-
-// The pass for a description with a Periodic part, any d: mll_grad_wide_kernel's two phases with
-// one wave-uniform branch per part on "is periodic".  cs: per part and point the unit features
-// [cos a_k | sin a_k], a_k = 2 pi x_k / p_k (launch_embed_unit; 2d wide, only Periodic parts'
-// rows are read) -- no pair evaluates a transcendental but the exponential.
+// PER: one wave-uniform branch per part on "is periodic"; the other parts run the two phases
+// above on raw x unchanged.  cs: per part and point the unit features [cos a_k | sin a_k],
+// a_k = 2 pi x_k / p_k (launch_embed_unit; 2d wide, only Periodic parts' rows are read) -- no
+// pair evaluates a transcendental but the exponential.
 // Periodic part, slots [S_sigma, S_l1..S_ld, S_p1..S_pd]:
 //  1. D = sum_k l_k^2 chord_k^2, chord_k^2 = (cos a - cos b)^2 + (sin a - sin b)^2
 //     = (2 sin(pi r_k / p_k))^2, GP dimensions at a time; weights mk = mv K_p as for SquaredExp;
@@ -313,49 +274,38 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
 //     the unrolled wave-uniform column loads cost 50 more SGPR spills for no fewer passes that
 //     matter):
 //     S_lk += mk chord_k^2, S_pk += mk r_k sin(a_k - b_k), sin(a - b) = sin a cos b - cos a sin b.
-// The other parts run the wide kernel's phases on raw x unchanged (slots [S_sigma, S_l1..S_ld]).
+constexpr int GW = 32;
 constexpr int GP = 8;
-template <bool MIX>
-__global__ __launch_bounds__(256) void mll_grad_per_kernel(KParams kp, const double* __restrict__ X,
-                                                           const double* __restrict__ cs, int n,
-                                                           const double* __restrict__ Kinv,
-                                                           size_t ldk, const double* __restrict__ alpha,
-                                                           double* __restrict__ partial, int nslot) {
+template <bool MIX, bool PER>
+__global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const double* __restrict__ X,
+                                                            const double* __restrict__ cs, int n,
+                                                            const double* __restrict__ Kinv,
+                                                            size_t ldk, const double* __restrict__ alpha,
+                                                            double* __restrict__ partial, int nslot) {
   __shared__ double red[4][GW + 2];
   __shared__ double tabs[KMAXP][256];  // sigma_p^2 2^(j/256)
   __shared__ double mks[16][256];      // mk_c of every thread
-  const int bid = blockIdx.x;
-  int bj = (int)((sqrt(8.0 * bid + 1.0) - 1.0) * 0.5);
-  while ((bj + 1) * (bj + 2) / 2 <= bid) ++bj;
-  while (bj * (bj + 1) / 2 > bid) --bj;
-  const int bi = bid - bj * (bj + 1) / 2;
-  const int i0 = bi * GT, j0 = bj * GT;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const GradTile g = grad_tile(n, Kinv, ldk, alpha);
   const int d = kp.dx, de = kp.de;
-  const int i = i0 + lane;
-  const bool irow = i < n;
-  const double wgt = (bi == bj) ? 1.0 : 2.0;
-  const size_t irc = (size_t)min(i, n - 1);
+  const int i = g.i, j0 = g.j0, wv = g.wv;
+  const bool irow = g.irow;
+  const double wgt = g.wgt, ai = g.ai;
+  const size_t irc = g.irc;
   const double* xrow = X + irc * d;
 
-  const double ai = irow ? alpha[i] : 0.0;
-  double s_wn = 0.0;
-  if (bi == bj && irow && ((lane - wv) & 3) == 0) s_wn = ai * ai - Kinv[(size_t)i + (size_t)i * ldk];
-
-  int slot = 0;
+  double* out = partial + (size_t)blockIdx.x * nslot;
   for (int p = 0; p < kp.nse; ++p) {
     if ((p & (KMAXP - 1)) == 0) {  // this group of parts' exp tables
       __syncthreads();
-      for (int g = p; g < min(kp.nse, p + KMAXP); ++g)
-        tabs[g - p][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
+      grad_fill_tabs(kp, p, tabs);
       __syncthreads();
     }
     const double* ts = tabs[p & (KMAXP - 1)];
     const double* l2p = kp.l2 + (size_t)p * d;
-    const bool per = __builtin_amdgcn_readfirstlane((int)kp.per[p]) != 0;
-    const double* csp = cs + (size_t)p * n * de;  // this part's unit features
-    const double* crow = csp + irc * de;
+    const bool per = PER && __builtin_amdgcn_readfirstlane((int)kp.per[p]) != 0;
+    // this part's unit features (cs is null without a Periodic part)
+    const double* csp = PER ? cs + (size_t)p * n * de : nullptr;
+    const double* crow = PER ? csp + irc * de : nullptr;
     // phase 1: the 16 weights.  A Periodic part's 16 distances first, GP dimensions of the row
     // point's cos / sin in registers at a time (the row point is read once per chunk, not once
     // per column), accumulated in the thread's own mks slots
@@ -398,10 +348,19 @@ __global__ __launch_bounds__(256) void mll_grad_per_kernel(KParams kp, const dou
       if (per) {
         dist = mks[c][threadIdx.x];
       } else {
-        double dpart[4] = {0.0, 0.0, 0.0, 0.0};
+        // D = sum_k l_k^2 r_k^2 in four partial sums, element k into dpart[k & 3]
         const double* xc = X + (size_t)j * d;
+        double dpart[4] = {0.0, 0.0, 0.0, 0.0};
+        int k = 0;
 #pragma unroll 1
-        for (int k = 0; k < d; ++k) {
+        for (; k + 4 <= d; k += 4) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const double r = xrow[k + u] - xc[k + u];
+            dpart[u] = fma(l2p[k + u], r * r, dpart[u]);
+          }
+        }
+        for (; k < d; ++k) {
           const double r = xrow[k] - xc[k];
           dpart[k & 3] = fma(l2p[k], r * r, dpart[k & 3]);
         }
@@ -416,16 +375,16 @@ __global__ __launch_bounds__(256) void mll_grad_per_kernel(KParams kp, const dou
     });
     for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
     if (per) {
-      // phase 2, Periodic: both sums of GP dimensions at a time
+      // phase 2, Periodic: both sums (acc[k], acc[GP + k]) of GP dimensions at a time
       for (int k0 = 0; k0 < d; k0 += GP) {
         const int kn = min(GP, d - k0);  // wave-uniform
-        double xr[GP], cr[GP], sr[GP], acc_l[GP], acc_p[GP];
+        double xr[GP], cr[GP], sr[GP], acc[2 * GP];
 #pragma unroll
         for (int k = 0; k < GP; ++k) {
           xr[k] = k < kn ? xrow[k0 + k] : 0.0;
           cr[k] = k < kn ? crow[k0 + k] : 0.0;
           sr[k] = k < kn ? crow[d + k0 + k] : 0.0;
-          acc_l[k] = acc_p[k] = 0.0;
+          acc[k] = acc[GP + k] = 0.0;
         }
 #pragma unroll 1
         for (int c = 0; c < 16; ++c) {
@@ -438,35 +397,17 @@ __global__ __launch_bounds__(256) void mll_grad_per_kernel(KParams kp, const dou
             const double cb = k < kn ? cc[k] : 0.0, sb = k < kn ? cc[d + k] : 0.0;
             const double r = xr[k] - (k < kn ? xc[k] : 0.0);
             const double dc = cr[k] - cb, ds = sr[k] - sb;
-            acc_l[k] = fma(mk, fma(dc, dc, ds * ds), acc_l[k]);
-            acc_p[k] = fma(mk * r, fma(sr[k], cb, -(cr[k] * sb)), acc_p[k]);
+            acc[k] = fma(mk, fma(dc, dc, ds * ds), acc[k]);
+            acc[GP + k] = fma(mk * r, fma(sr[k], cb, -(cr[k] * sb)), acc[GP + k]);
           }
         }
-#pragma unroll
-        for (int k = 0; k < GP; ++k)
-          for (int o = 32; o > 0; o >>= 1) {
-            acc_l[k] += __shfl_xor(acc_l[k], o);
-            acc_p[k] += __shfl_xor(acc_p[k], o);
-          }
-        __syncthreads();
-        if (lane == 0) {
-          red[wv][0] = acc_s;
-#pragma unroll
-          for (int k = 0; k < GP; ++k) {
-            red[wv][1 + k] = acc_l[k];
-            red[wv][1 + GP + k] = acc_p[k];
-          }
-        }
-        __syncthreads();
         // slot 0 of the part (S_sigma) with the first chunk, then this chunk's kn + kn sums
-        for (int t = threadIdx.x + (k0 ? 1 : 0); t < 1 + 2 * GP; t += 256) {
-          const int k = t == 0 ? 0 : (t - 1) % GP;
-          if (t > 0 && k >= kn) continue;
-          const int dst = t == 0 ? 0 : t <= GP ? 1 + k0 + k : 1 + d + k0 + k;
-          partial[(size_t)bid * nslot + slot + dst] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
-        }
+        grad_reduce(g.lane, g.wv, acc_s, acc, red, k0 ? 1 : 0, 1 + 2 * GP, out, [&](int t) {
+          const int k = (t - 1) % GP;
+          return t == 0 ? 0 : k >= kn ? -1 : t <= GP ? 1 + k0 + k : 1 + d + k0 + k;
+        });
       }
-      slot += 2 * d + 1;
+      out += 2 * d + 1;
       continue;
     }
     // phase 2: the length-scale sums, GW dimensions at a time
@@ -489,28 +430,13 @@ __global__ __launch_bounds__(256) void mll_grad_per_kernel(KParams kp, const dou
           acc_l[k] = fma(mk, r * r, acc_l[k]);
         }
       }
-#pragma unroll
-      for (int k = 0; k < GW; ++k)
-        for (int o = 32; o > 0; o >>= 1) acc_l[k] += __shfl_xor(acc_l[k], o);
-      __syncthreads();
-      if (lane == 0) {
-        red[wv][0] = acc_s;
-#pragma unroll
-        for (int k = 0; k < GW; ++k) red[wv][1 + k] = acc_l[k];
-      }
-      __syncthreads();
-      for (int t = threadIdx.x + (k0 ? 1 : 0); t < kn + 1; t += 256)
-        partial[(size_t)bid * nslot + slot + (t ? k0 + t : 0)] =
-            red[0][t] + red[1][t] + red[2][t] + red[3][t];
+      // slot 0 of the part (S_sigma) with the first chunk, then this chunk's kn sums
+      grad_reduce(g.lane, g.wv, acc_s, acc_l, red, k0 ? 1 : 0, kn + 1, out,
+                  [&](int t) { return t ? k0 + t : 0; });
     }
-    slot += d + 1;
+    out += d + 1;
   }
-  for (int o = 32; o > 0; o >>= 1) s_wn += __shfl_xor(s_wn, o);
-  __syncthreads();
-  if (lane == 0) red[wv][GW + 1] = s_wn;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    partial[(size_t)bid * nslot + slot] = red[0][GW + 1] + red[1][GW + 1] + red[2][GW + 1] + red[3][GW + 1];
+  grad_store_wn(g, red, out);
 }
 
 // out[slot] = sum_b partial[b][slot]  (fixed order)
@@ -529,24 +455,31 @@ __global__ void reduce_partials_kernel(const double* __restrict__ partial, int n
   if (threadIdx.x == 0) out[slot] = red[0];
 }
 
-template <int D>
-int launch_grad_tiles(gpr_ctx* ctx, const KParams& kp, const double* X, int n, const double* Kinv,
-                      int ldk, const double* alpha, double* partial, int nslot, long long nblk) {
-  if (kp.mix) {
-    if (kp.d == D)
-      mll_grad_tiles_kernel<D, true, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-          kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
-    else
-      mll_grad_tiles_kernel<D, false, true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-          kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
-  } else if (kp.d == D)
-    mll_grad_tiles_kernel<D, true, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-        kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
+// The gradient pass of one description into partial[nblk][nslot]: a Periodic part takes the wide
+// kernel's PER form on the unit features cs; else the kernel compiled for the next D >= d (EXACT
+// where d == D) up to d = 32, the wide kernel above.
+template <bool MIX>
+void launch_grad_pass(gpr_ctx* ctx, const KParams& kp, const double* X, const double* cs, int n,
+                      const double* Kinv, int ldk, const double* alpha, double* partial, int nslot,
+                      long long nblk) {
+  const int d = kp.d;
+  const unsigned grid = (unsigned)nblk;
+  auto tiles = [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    auto* k = d == D ? &mll_grad_tiles_kernel<D, true, MIX> : &mll_grad_tiles_kernel<D, false, MIX>;
+    k<<<grid, 256, 0, ctx->stream>>>(kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
+  };
+  if (kp.nper)
+    mll_grad_wide_kernel<MIX, true><<<grid, 256, 0, ctx->stream>>>(kp, X, cs, n, Kinv, (size_t)ldk,
+                                                                    alpha, partial, nslot);
+  else if (d <= 2) tiles(std::integral_constant<int, 2>{});
+  else if (d <= 4) tiles(std::integral_constant<int, 4>{});
+  else if (d <= 8) tiles(std::integral_constant<int, 8>{});
+  else if (d <= 16) tiles(std::integral_constant<int, 16>{});
+  else if (d <= 32) tiles(std::integral_constant<int, 32>{});
   else
-    mll_grad_tiles_kernel<D, false, false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-        kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
-  LAUNCH_CHECK(ctx);
-  return 0;
+    mll_grad_wide_kernel<MIX, false><<<grid, 256, 0, ctx->stream>>>(kp, X, nullptr, n, Kinv,
+                                                                     (size_t)ldk, alpha, partial, nslot);
 }
 
 }  // namespace
@@ -582,29 +515,12 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   double* sums = ctx->dscratch + (size_t)nblk * nslot;
   {
     TimerScope ts(ctx, TC_OTHER, 0.0);
-    if (kp.nper) {
-      GPR_TRY(launch_embed_unit(ctx, kp, dX, n));
-      if (kp.mix)
-        mll_grad_per_kernel<true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-            kp, dX, ctx->dxs, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
-      else
-        mll_grad_per_kernel<false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-            kp, dX, ctx->dxs, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
-      LAUNCH_CHECK(ctx);
-    } else if (d <= 2) GPR_TRY(launch_grad_tiles<2>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
-    else if (d <= 4) GPR_TRY(launch_grad_tiles<4>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
-    else if (d <= 8) GPR_TRY(launch_grad_tiles<8>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
-    else if (d <= 16) GPR_TRY(launch_grad_tiles<16>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
-    else if (d <= 32) GPR_TRY(launch_grad_tiles<32>(ctx, kp, dX, n, dKinv, ldk, dalpha, partial, nslot, nblk));
-    else {
-      if (kp.mix)
-        mll_grad_wide_kernel<true><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-            kp, dX, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
-      else
-        mll_grad_wide_kernel<false><<<(unsigned)nblk, 256, 0, ctx->stream>>>(
-            kp, dX, n, dKinv, (size_t)ldk, dalpha, partial, nslot);
-      LAUNCH_CHECK(ctx);
-    }
+    if (kp.nper) GPR_TRY(launch_embed_unit(ctx, kp, dX, n));  // (into ctx->dxs)
+    kmix_dispatch(kp.mix, [&](auto mix) {
+      launch_grad_pass<decltype(mix)::value>(ctx, kp, dX, ctx->dxs, n, dKinv, ldk, dalpha, partial,
+                                             nslot, nblk);
+    });
+    LAUNCH_CHECK(ctx);
   }
   reduce_partials_kernel<<<nslot, 256, 0, ctx->stream>>>(partial, (int)nblk, nslot, sums);
   LAUNCH_CHECK(ctx);
@@ -613,7 +529,6 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // assemble in hp order (kinds order)
   int off = 0, so = 0;
-  bool noise_seen = false;
   for (int t = 0; t < nk; ++t) {
     if (kinds[t] != GPR_WN) {
       const double* ss = s.data() + so;
@@ -630,7 +545,6 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
     } else {
       // every WhiteNoise part's gradient is 2 sigma_n I (src/deriv_covar.jl:31-32)
       grad[off] = -0.5 * (2.0 * hp[off]) * s[nslot - 1];
-      (void)noise_seen;
       off += 1;
     }
   }
