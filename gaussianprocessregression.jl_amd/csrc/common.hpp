@@ -200,7 +200,14 @@ struct gpr_ctx {
   long long dag_spin_limit = 1ll << 25;  // DAG dependency wait bound in polls (~4 s); test
                                         // builds let GPR_DAG_SPIN_LIMIT override it per launch
   int dag_zlag = 4;       // lower-triangular right-hand-side rows scheduled after A's row i + lag (GPR_DAG_ZLAG)
-  int dag_lag_built = -1;
+  // plain launches' ticket order (dag.hip dag_task_order): rows taken dag_rgroup at a time
+  // (GPR_DAG_RGROUP: 1 row order, 2, 4) from row dag_rgroup_min on (GPR_DAG_RGROUP_MIN), a
+  // group's tasks merged by column with member r dag_rskew column slots behind member r - 1
+  // (GPR_DAG_RSKEW), so the readers of a column panel run close together
+  // Measured (C3 job, one box, alternating): group 1 292.0-294.2 ms per step, 2 289.8, 4 284.3-
+  // 285.5, 8 289.9-290.1 (tried, not kept); every skew > 0 slower than skew 0; gmin 0 = 32.
+  int dag_rgroup = 4, dag_rskew = 0, dag_rgroup_min = 32;
+  int dag_order_built[4] = {-1, -1, -1, -1};  // (zlag, rgroup, rskew, rgroup_min) of dag_tasks
   // one-shot hook of the next whole-matrix factorisation launch (kglob 0, not a solve), called
   // right after the kernel is enqueued with an event that completes once the launch's progress
   // counters are reset (null if it could not be made): work ordered behind that event runs

@@ -23,7 +23,8 @@
 //
 // Scheduling: one workgroup per CU (the CU's whole 160 KB of LDS: a ring of five 32-KB DMA
 // stages of the GEMM pipeline, or the diagonal block), tasks claimed from an atomic ticket in
-// a host-built topological order (row i of A's tiles, then row i of B's, i = 0, 1, ...): every
+// a host-built topological order (row i of A's tiles, then row i of B's, i = 0, 1, ...; plain
+// launches take the rows in groups merged by column, dag_task_order below): every
 // tile a task waits for belongs to an earlier ticket, i.e. to a workgroup that is already
 // running, so the grid cannot deadlock whatever the residency.  Every wait is bounded
 // (~seconds): on timeout the launch flags info = -1 and every task still publishes, so the
@@ -804,6 +805,88 @@ extern "C" int gpr_debug_dag_shape_ok(int n, int lda, unsigned long long addr) {
   return dag_shape_ok(n, lda, reinterpret_cast<const double*>((uintptr_t)addr)) ? 1 : 0;
 }
 
+// The ticket order of a launch: the task codes (bit 31: right-hand-side tile, bits 16-30: tile
+// row i, bits 0-15: column tile) in the order the workgroups claim them, then G's tiles.
+//
+// group = 1: row order.  A's row i, then the right-hand-side row i - lag: a lower-triangular
+// B's tiles (i, c) near the diagonal accumulate only i - c row blocks and would otherwise sit
+// waiting for W_i (the diagonal task of the same row, still accumulating i blocks).
+// (a lag for the other right-hand sides, 1, 2 or 4 rows, measured no faster for C2 / C3)
+//
+// group = R > 1 (plain launches only: not lower, not gram): rows below gmin (rounded up to a
+// multiple of R) keep row order; from there on R rows share their tickets.  The task of
+// (i, j) streams column panel j, rows k < i, which no other task of row i reads; the task
+// (i + 1, j) reads the same panel one block longer.  Inside a group the tasks are merged by
+// column -- member r's task for column j sits r * skew column slots behind member 0's task for
+// column j, ties to the lower row first -- so the readers of a panel run a few microseconds
+// apart and the second is served on-die.  A's tiles of the group first, then its
+// right-hand-side tiles under the same rule (a solve-only launch has only these; their panel
+// is B's column).  A pair gives F(2m), T(2m, 2m+1), F(2m+1), T(2m, 2m+2), T(2m+1, 2m+2), ...
+//
+// Every order is topological, and the launch's deadlock-freedom argument is exactly that:
+// every tile a task reads has an earlier ticket -- (k, i) and (k, j) for k < i, and (i, i)
+// for an off-diagonal task.  In a group, (k, .) of an earlier group or an ungrouped row comes
+// before the whole group; of member r' < r of the same group, (g + r', j) sits (r - r') * skew
+// >= 0 slots ahead of (g + r, j) with the tie to the lower row, and (g + r', g + r) and the
+// diagonal (g + r, g + r) sit at slots r + r' * skew <= r + r * skew, no later than any task
+// of member r (whose first column is g + r).
+std::vector<unsigned> dag_task_order(int nt, int ntr, bool solve, bool lower, bool gram, int zlag,
+                                     int group, int skew, int gmin) {
+  std::vector<unsigned> tasks;
+  tasks.reserve((size_t)nt * (nt + 1) + (size_t)nt * ntr);
+  const int lag = solve || !lower ? 0 : std::min(std::max(zlag, 0), nt);
+  auto a_task = [&](int i, int j) { tasks.push_back(((unsigned)i << 16) | (unsigned)j); };
+  auto rhs_task = [&](int i, int c) {
+    tasks.push_back(0x80000000u | ((unsigned)i << 16) | (unsigned)c);
+  };
+  auto rhs_row = [&](int i) {
+    for (int c = 0; c < (lower ? std::min(ntr, i + 1) : ntr); ++c) rhs_task(i, c);
+  };
+  const int R = (lower || gram || group < 2) ? 1 : (group < 4 ? 2 : 4);
+  // first grouped row; a skew of a whole row or more is row order, whatever its value
+  const int g0 = R == 1 ? nt : (int)std::min<long long>(nt, ((long long)std::max(gmin, 0) + R - 1) / R * R);
+  const int sk = std::min(std::max(skew, 0), std::max(nt, ntr));
+  // (the diagonal task F(i + 1) right behind T(i, i + 1) instead of behind all of row i
+  // measured within 0.1-0.4 % either way for C2 / C3 / C4, so row order it is)
+  for (int i = 0; i < g0; ++i) {
+    if (!solve)
+      for (int j = i; j < nt; ++j) a_task(i, j);
+    if (i - lag >= 0) rhs_row(i - lag);
+  }
+  for (int i = std::max(nt - lag, 0); i < nt; ++i) rhs_row(i);  // (lag > 0: R = 1)
+  for (int g = g0; g < nt; g += R) {
+    const int m = std::min(R, nt - g);  // (a partial last group)
+    if (!solve)
+      for (int s = 0; s < nt - g + (m - 1) * sk; ++s)
+        for (int r = 0; r < m; ++r) {
+          const int j = g + s - r * sk;
+          if (j >= g + r && j < nt) a_task(g + r, j);
+        }
+    for (int s = 0; s < ntr + (m - 1) * sk; ++s)
+      for (int r = 0; r < m; ++r) {
+        const int c = s - r * sk;
+        if (c >= 0 && c < ntr) rhs_task(g + r, c);
+      }
+  }
+  // G's upper tiles last, by column: G_ij sums B's row blocks k >= j, so the low columns
+  // (the longest sums, whose first blocks are final earliest) go first
+  if (gram)
+    for (int j = 0; j < nt; ++j)
+      for (int i = 0; i <= j; ++i) a_task(i, j);
+  return tasks;
+}
+
+// (tests: the order itself, host only -- no HIP call.  flags: DAG_SOLVE | DAG_LOWER | DAG_GRAM.
+// Writes the first min(count, cap) codes to out and returns the count.)
+extern "C" int gpr_debug_dag_task_order(int nt, int ntr, int flags, int zlag, int group, int skew,
+                                        int gmin, unsigned* out, int cap) {
+  if (nt <= 0 || nt > 32767 || ntr < 0 || ntr > 65535) return -1;
+  const std::vector<unsigned> t = dag_task_order(nt, ntr, flags & DAG_SOLVE, flags & DAG_LOWER,
+                                                 flags & DAG_GRAM, zlag, group, skew, gmin);
+  for (size_t k = 0; k < t.size() && (long long)k < cap; ++k) out[k] = t[k];
+  return (int)t.size();
+}
+
 // true when potrf_core factors (n, lda, dA) as one tile-DAG launch: directly, or for any other
 // shape through a padded copy (dag_padded)
 bool dag_takes_whole(const gpr_ctx* ctx, int n, int lda, const double* dA) {
@@ -894,33 +977,12 @@ int launch_potrf_dag(gpr_ctx* ctx, double* dA, int n, int lda, double* dB, int n
     return 1;
   const int nt = (n + DT - 1) / DT, ntr = dB ? (nrhs + DT - 1) / DT : 0;
   GPR_TRY(ensure_winv(ctx, kglob + n, DT));
+  const int key[4] = {ctx->dag_zlag, ctx->dag_rgroup, ctx->dag_rskew, ctx->dag_rgroup_min};
   if (ctx->dag_nt != nt || ctx->dag_ntr != ntr || ctx->dag_flags != (flags & ~DAG_MIRROR) ||
-      ctx->dag_lag_built != ctx->dag_zlag) {
-    std::vector<unsigned> tasks;
-    tasks.reserve((size_t)nt * (nt + 1) + (size_t)nt * ntr);
-    // right-hand-side row i after A's row i + lag: a lower-triangular B's tiles (i, c) near
-    // the diagonal accumulate only i - c row blocks and would otherwise sit waiting for W_i
-    // (the diagonal task of the same row, still accumulating i blocks); the order stays
-    // topological (every dependency of a task has an earlier ticket)
-    // (a lag for the other right-hand sides, 1, 2 or 4 rows, measured no faster for C2 / C3)
-    const int lag = solve || !lower ? 0 : std::min(ctx->dag_zlag, nt);
-    auto rhs_row = [&](int i) {
-      for (int c = 0; c < (lower ? std::min(ntr, i + 1) : ntr); ++c)
-        tasks.push_back(0x80000000u | ((unsigned)i << 16) | (unsigned)c);
-    };
-    // (the diagonal task F(i + 1) right behind T(i, i + 1) instead of behind all of row i
-    // measured within 0.1-0.4 % either way for C2 / C3 / C4, so row order it is)
-    for (int i = 0; i < nt; ++i) {
-      if (!solve)
-        for (int j = i; j < nt; ++j) tasks.push_back(((unsigned)i << 16) | (unsigned)j);
-      if (i - lag >= 0) rhs_row(i - lag);
-    }
-    for (int i = std::max(nt - lag, 0); i < nt; ++i) rhs_row(i);
-    // G's upper tiles last, by column: G_ij sums B's row blocks k >= j, so the low columns
-    // (the longest sums, whose first blocks are final earliest) go first
-    if (gram)
-      for (int j = 0; j < nt; ++j)
-        for (int i = 0; i <= j; ++i) tasks.push_back(((unsigned)i << 16) | (unsigned)j);
+      !std::equal(key, key + 4, ctx->dag_order_built)) {
+    // the topological ticket order (dag_task_order above): row order, or rows in groups
+    const std::vector<unsigned> tasks =
+        dag_task_order(nt, ntr, solve, lower, gram, key[0], key[1], key[2], key[3]);
     // a previous launch on this context may still be reading the old list (a factorisation
     // launch returns without synchronising; a solve-only launch syncs to read its info, but
     // the list may belong to a factorisation): drain the context's stream before freeing it
@@ -937,7 +999,7 @@ int launch_potrf_dag(gpr_ctx* ctx, double* dA, int n, int lda, double* dB, int n
     ctx->dag_nt = nt;
     ctx->dag_ntr = ntr;
     ctx->dag_flags = flags & ~DAG_MIRROR;  // (the task list does not depend on it)
-    ctx->dag_lag_built = ctx->dag_zlag;
+    std::copy(key, key + 4, ctx->dag_order_built);
   }
   // a previous launch's hook may have left readers of the counters (row gates on another
   // stream): they must drain before the counters are reset or reallocated

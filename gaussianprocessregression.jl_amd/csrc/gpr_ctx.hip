@@ -231,6 +231,9 @@ const Knob kKnobs[] = {
     {"GPR_DAG_SOLVE", &gpr_ctx::dag_solve, nullptr},
     {"GPR_DAG_GRAM", &gpr_ctx::dag_gram, nullptr},
     {"GPR_DAG_ZLAG", &gpr_ctx::dag_zlag, nullptr},
+    {"GPR_DAG_RGROUP", &gpr_ctx::dag_rgroup, nullptr},
+    {"GPR_DAG_RSKEW", &gpr_ctx::dag_rskew, nullptr},
+    {"GPR_DAG_RGROUP_MIN", &gpr_ctx::dag_rgroup_min, nullptr},
     {"GPR_FUSED_RHS", &gpr_ctx::fused_rhs, nullptr},
     {"GPR_FUSE_Y", &gpr_ctx::fuse_y, nullptr},
     {"GPR_FUSE_KINV", &gpr_ctx::fuse_kinv, nullptr},
@@ -251,6 +254,8 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
   if (k.ip) {
     int iv = (int)v;
     if (k.ip == &gpr_ctx::dag_zlag) iv = std::max(0, iv);
+    if (k.ip == &gpr_ctx::dag_rgroup) iv = iv < 2 ? 1 : (iv < 4 ? 2 : 4);
+    if (k.ip == &gpr_ctx::dag_rskew || k.ip == &gpr_ctx::dag_rgroup_min) iv = std::max(0, iv);
     if (k.ip == &gpr_ctx::cv_streams) iv = std::max(1, std::min(iv, (int)gpr_ctx::CV_MAX_SUB));
     ctx->*k.ip = iv;
   } else {
@@ -442,7 +447,8 @@ int gpr_set_knob(gpr_ctx_t ctx, const char* name, double value) {
   const Knob* k = knob_find(name);
   if (!k) return set_err(ctx, GPR_E_ARG, "unknown knob %s", name ? name : "(null)");
   knob_set(ctx, *k, value);
-  if (k->ip == &gpr_ctx::dag_zlag) ctx->dag_lag_built = -1;  // (the task list depends on it)
+  // (the cached task list depends on GPR_DAG_ZLAG / RGROUP / RSKEW / RGROUP_MIN: the next
+  // launch compares all four with the values the list was built from and rebuilds it)
   return 0;
 }
 

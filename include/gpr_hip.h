@@ -138,6 +138,16 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         (-1 auto: n >= 8192 with >= n right-hand sides; 0 never; 1 always)
  *   GPR_DAG_GRAM       1  gpr_fit_kinv: K^{-1} = Z^T Z as gram tasks of the DAG launch
  *   GPR_DAG_ZLAG       4  DAG: Z = U^{-T}'s row i scheduled after A's row i + lag
+ *   GPR_DAG_RGROUP     4  DAG ticket order of plain launches (factorisation with general
+ *                         right-hand sides, solve-only): tile rows taken 1 (row order), 2 or 4
+ *                         at a time (other values round down), a group's tasks merged by column
+ *                         so the readers of a column panel run together; lower-triangular /
+ *                         gram / batched launches keep row order.  Results are bit for bit the
+ *                         same for every value.  Measured, C3 job: 293.0 (1) -> 286.0 ms (4)
+ *   GPR_DAG_RSKEW      0  ... member r of a group r * skew column slots behind member 0
+ *                         (every skew > 0 measured slower)
+ *   GPR_DAG_RGROUP_MIN 32 ... first grouped tile row (rounded up to a multiple of the group;
+ *                         launches of fewer tile rows keep row order)
  *   GPR_FUSED_RHS     -1  gpr_fit_predict: [K(x, xp) | y] solved inside the factorisation
  *                         (-1 auto, 0 after it, 1 own stream, 2 main stream; blocked path)
  *   GPR_FUSE_Y         1  gpr_fit: z = U^{-T} y inside the factorisation

@@ -1,8 +1,9 @@
 // Watchdog harness for the tile-DAG factorisation (dag.hip built with -DDAG_TRACE): runs
 // gpr_potrf_upper on a diagonally dominant SPD matrix in a thread and prints the
 // per-workgroup progress words while it runs; exits (code 3) if it has not finished in 10 s.
-// usage: dag_probe N [np]   (np > 0: the C3-style job; np < 0: the C4-style gpr_fit_kinv,
-// SE+WN, d = 16 -- factorisation, Z = U^-T and K^-1 = Z^T Z in the one launch)
+// usage: dag_probe N [np [rgroup [rskew [rgroup_min]]]]   (np > 0: the C3-style job; np < 0: the
+// C4-style gpr_fit_kinv, SE+WN, d = 16 -- factorisation, Z = U^-T and K^-1 = Z^T Z in the one
+// launch; np = 0: the factorisation alone)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +25,15 @@ int main(int argc, char** argv) {
   setenv("GPR_DAG", "1", 1);
   gpr_ctx_t ctx;
   if (gpr_ctx_create(0, nullptr, &ctx)) return 1;
+  // the ticket order's knobs: from the environment like every knob, or argv[3..5] = row group,
+  // skew, first grouped row (the phase profile per setting in one script)
+  const char* order_knobs[3] = {"GPR_DAG_RGROUP", "GPR_DAG_RSKEW", "GPR_DAG_RGROUP_MIN"};
+  for (int k = 0; k < 3; ++k) {
+    if (argc > 3 + k) gpr_set_knob(ctx, order_knobs[k], atof(argv[3 + k]));
+    double v = 0;
+    gpr_get_knob(ctx, order_knobs[k], &v);
+    printf("%s=%d%s", order_knobs[k], (int)v, k < 2 ? " " : "\n");
+  }
   std::vector<double> h((size_t)n * n);
   for (int j = 0; j < n; ++j)
     for (int i = 0; i < n; ++i) h[(size_t)j * n + i] = (i == j) ? n + 1.0 : 1.0 / (1 + i + j);
