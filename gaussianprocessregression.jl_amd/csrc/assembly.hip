@@ -1511,14 +1511,19 @@ int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n
   return 0;
 }
 
-int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n) {
+int launch_embed_unit_to(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double** buf,
+                         size_t* cap) {
   if (!kp.nper || n <= 0) return 0;
-  GPR_TRY(ensure_buf(ctx, &ctx->dxs, &ctx->xs_cap, (size_t)kp.nse * kp.de * n + 1));
+  GPR_TRY(ensure_buf(ctx, buf, cap, (size_t)kp.nse * kp.de * n + 1));
   const size_t total = (size_t)kp.nse * kp.dx * n;
   const int blocks = (int)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 4096));
-  embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 1, ctx->dxs);
+  embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 1, *buf);
   LAUNCH_CHECK(ctx);
   return 0;
+}
+
+int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n) {
+  return launch_embed_unit_to(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap);
 }
 
 int launch_pair(gpr_ctx* ctx, int mode, int d, const double* xa, int na, const double* xb, int nb,

@@ -159,7 +159,8 @@ struct KParBlock {
 // site), recorded in addition to the call-site class.
 enum TimingClass {
   TC_KBUILD = 0, TC_SYRK = 1, TC_PANEL = 2, TC_TRSM_GEMM = 3, TC_OTHER = 4, TC_GEMM_PIPE = 5,
-  TC_DAG = 6, TC_DAG_SOLVE = 7, TC_N = 8
+  TC_DAG = 6, TC_DAG_SOLVE = 7, TC_PGRAD_MEAN = 8, TC_PGRAD_VAR = 9, TC_PGRAD_SOLVE = 10,
+  TC_N = 11
 };
 
 struct TimedLaunch {
@@ -329,6 +330,11 @@ struct gpr_ctx {
   double quad_batch_gb = 16.0;  // GPR_QUAD_BATCH_GB: the same for the quadrature's columns
   int quad_eigen = -1;          // GPR_QUAD_EIGEN: sample_noise quadrature path (-1 auto)
   int quad_seq = 0;             // GPR_QUAD_SEQ=1: its per-column factorisations one at a time
+  int pgrad_slab = 1024;        // GPR_PGRAD_SLAB: training points per workgroup of the posterior-
+                                // gradient passes (predict_grad.hip; rounded up to a multiple of 64)
+  int pgrad_solve = -1;         // GPR_PGRAD_SOLVE: Q = K^{-1} K(x, xp) of the variance gradient by
+                                // potrs_core's sweeps (0), by Z = U^{-T} and two MFMA products (1),
+                                // -1 auto (predict_grad.hip)
 
   bool timing = false;
   std::vector<TimedLaunch> pending;
@@ -437,6 +443,9 @@ int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n
 // l_k) for the Periodic parts of kp (the other parts' rows are not for use); the MLL gradient's
 // per-point table
 int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n);
+// the same into *buf (grown to nse x 2d x n doubles): the posterior gradient's training and test points
+int launch_embed_unit_to(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double** buf,
+                         size_t* cap);
 int launch_pair(gpr_ctx* ctx, int mode, int d, const double* xa, int na, const double* xb, int nb,
                 double s2, double* out, size_t sa, size_t sb);
 int launch_set_identity(gpr_ctx* ctx, double* A, int n, int lda);

@@ -248,6 +248,8 @@ const Knob kKnobs[] = {
     {"GPR_QUAD_BATCH_GB", nullptr, &gpr_ctx::quad_batch_gb},
     {"GPR_QUAD_EIGEN", &gpr_ctx::quad_eigen, nullptr},
     {"GPR_QUAD_SEQ", &gpr_ctx::quad_seq, nullptr},
+    {"GPR_PGRAD_SLAB", &gpr_ctx::pgrad_slab, nullptr},
+    {"GPR_PGRAD_SOLVE", &gpr_ctx::pgrad_solve, nullptr},
 };
 
 void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
@@ -257,6 +259,7 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
     if (k.ip == &gpr_ctx::dag_rgroup) iv = iv < 2 ? 1 : (iv < 4 ? 2 : 4);
     if (k.ip == &gpr_ctx::dag_rskew || k.ip == &gpr_ctx::dag_rgroup_min) iv = std::max(0, iv);
     if (k.ip == &gpr_ctx::cv_streams) iv = std::max(1, std::min(iv, (int)gpr_ctx::CV_MAX_SUB));
+    if (k.ip == &gpr_ctx::pgrad_slab) iv = (std::max(iv, 64) + 63) / 64 * 64;
     ctx->*k.ip = iv;
   } else {
     ctx->*k.dp = v;

@@ -39,6 +39,8 @@ from .core import (
     loss_grad_,
     predict,
     predict_,
+    predict_grad,
+    predict_grad_,
     predict_mean,
     predict_mean_,
     split_factors,

@@ -759,6 +759,51 @@ def predict_mean_(mu: torch.Tensor, md: GPRModel, xp, pc: GPRPredictCache,
     predict_(mu, None, md, xp, pc, True, mean_only=True, eps=eps)
 
 
+def _no_cmap(xp):
+    if isinstance(xp, Cmap):
+        raise TypeError("predict_grad takes test points as a d x np array: split (Cmap) prediction "
+                        "has no gradient path (use cm.points() for the grid's points)")
+
+
+def predict_grad_(dmu: torch.Tensor, dvar: Optional[torch.Tensor], md: GPRModel, xp,
+                  pc: GPRPredictCache, eps: float = EPS_DEFAULT):
+    """Gradients of the posterior mean and diagonal variance with respect to the test inputs, on
+    device buffers from an updated cache (gpr_predict_grad; nothing is refitted -- the form an
+    optimisation loop over xp calls).  dmu: (np, d), or (ny, np, d) for a 2-D y -- column-major
+    d x np [x ny], a test point's gradient contiguous; dvar: (np, d) or None.  Always the cross
+    kernel: ``xp is md.x`` gets no same-object treatment here."""
+    _no_cmap(xp)
+    ctx = md.ctx
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(md.params)
+    dxp = _dxp(md, xp)
+    m = dxp.shape[0]
+    if dvar is not None and pc.Kxp.numel() < m * md.n:
+        pc.Kxp = ctx.empty(m, md.n)
+    ctx.check(lib.gpr_predict_grad(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(pc.Kxx),
+                                   md.n, _ptr(pc.wt), pc.nrhs, _ptr(dxp), m,
+                                   0 if dvar is None else 1, eps, _ptr(dmu), _ptr(dvar),
+                                   _ptr(pc.Kxp) if dvar is not None else None), "gpr_predict_grad")
+
+
+def predict_grad(md: GPRModel, xp, var: bool = True, eps: float = EPS_DEFAULT):
+    """(dmu, dvar): d mu(xp_j) / d xp_kj and d sigma^2(xp_j) / d xp_kj of predict(md, xp;
+    diagonal_var=true), shaped like xp: (d, np) each -- dmu (ny, d, np) for a 2-D y; dvar is
+    None with var=False.  Fits like predict_mean, then one gpr_predict_grad."""
+    _no_cmap(xp)
+    ctx = md.ctx
+    m = np.asarray(xp).shape[-1]
+    pc = GPRPredictCache(md, m if var else 0)
+    _update_predict_cache(pc, md, eps)
+    dmu = ctx.empty(pc.nrhs, m, md.d) if md.y.ndim == 2 else ctx.empty(m, md.d)
+    dvar = ctx.empty(m, md.d) if var else None
+    predict_grad_(dmu, dvar, md, xp, pc, eps)
+    ctx.sync()
+    gm = dmu.cpu().numpy()
+    gm = gm.transpose(0, 2, 1).copy() if gm.ndim == 3 else gm.T.copy()
+    return gm, (ctx.host(dvar) if var else None)
+
+
 def similar(md: GPRModel, hp, x, y) -> GPRModel:
     """similar(md, hp, x, y) (src/models.jl:47-49): same kernel, new data."""
     return GPRModel(md.covar, hp, x, y, train_axis=md.train_axis, ctx=md.ctx)

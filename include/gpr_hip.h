@@ -86,6 +86,14 @@ extern "C" {
  * Every per-stationary-part rule above holds for a Periodic part unchanged (LogScale's G .*= hp
  * covers the p entries).
  *
+ * Derivatives with respect to an input (gpr_predict_grad), for the cross kernel k(x*, x) of a
+ * test point x* and a training point x, r_k = x*_k - x_k on raw x:
+ *   dk/dx*_k = -W dD/dx*_k,
+ *   GPR_SE / GPR_M32 / GPR_M52   dD/dx*_k = 2 l_k^2 r_k
+ *   GPR_PER                      dD/dx*_k = (4 pi l_k^2 / p_k) sin(2 pi r_k / p_k)
+ * with W as above (GPR_PER: W = k).  A Matern part at a coincident point has a finite W and
+ * r = 0, so the term is 0.  A WhiteNoise part contributes nothing: the cross kernel has no noise.
+ *
  * Calls built on SquaredExp's separability or its closed-form erf integrals refuse a description
  * with a Matern or Periodic part -- GPR_E_UNSUP, the message names the part, nothing is computed or written:
  * gpr_split_predict, gpr_split_predict_rows, gpr_split_predict_shard, gpr_split_predict_mgpu,
@@ -125,7 +133,9 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *        3 TRSM trailing GEMM, 4 other (call-site classes), 5 every launch of the
  *        pipelined MFMA GEMM kernel (kernel-level, overlaps 1-4), 6 tile-DAG factorisation
  *        launches (with any right-hand sides they solve), 7 solve-only tile-DAG launches
- *        (U^{-T} B from a finished factor: C5's variance rows, POTRI's Z).
+ *        (U^{-T} B from a finished factor: C5's variance rows, POTRI's Z), 8 / 9 the mean /
+ *        variance pass of gpr_predict_grad (its kernels and their fixed-order sum), 10 the solve
+ *        that makes its Q (call-level: the launches inside it also count in their own classes).
  *        Returns accumulated ms, launch count, flops (bytes for class 0). */
 /* Knobs: the library's run-time switches.  Each is a GPR_* environment variable read ONCE,
  * when a context is created, and can be changed on a live context with gpr_set_knob (values
@@ -172,6 +182,14 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         comparator, exists only in the test build libgpr_hip_testing.so)
  *   GPR_QUAD_BATCH_GB 16  device-memory budget of one batched quadrature launch
  *   GPR_QUAD_SEQ       0  1: the per-column factorisations one at a time (no batch)
+ *   GPR_PGRAD_SLAB  1024  gpr_predict_grad: training points per workgroup (the slab whose partial
+ *                         sums a workgroup writes; rounded up to a multiple of 64, at least 64).
+ *                         Changes how the sum over the training points is cut, nothing else
+ *   GPR_PGRAD_SOLVE   -1  gpr_predict_grad, want_var: Q = K^{-1} K(x, xp) by gpr_potrs_upper's
+ *                         sweeps (0: one pass over U per two columns) or by Z = U^{-T} and two
+ *                         MFMA products, Q = Z^T (U^{-T} K(x, xp)) (1: n^2 + n m doubles of
+ *                         workspace); -1 auto: the products for m > max(16, n / 512).  Measured at
+ *                         n = 32768, m = 8192: 26.7 s by the sweeps, 535 ms by the products
  * A gpr_mgpu handle has knobs of its own, read from the environment once at gpr_mgpu_create
  * and changed with gpr_mgpu_set_knob / gpr_mgpu_get_knob (below):
  *   GPR_MGPU_STREAM   -1  1: stream U out during device 0's fit; 0: after it (-1 auto: only
@@ -283,6 +301,30 @@ int gpr_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d
                 const double* dX, int n, const double* dU, int ldu, const double* dwt,
                 int nrhs, const double* dXp, int m, int mode, double eps, double* dmu,
                 double* dvar, int ldv, double* dwork);
+
+/* Gradients of the posterior w.r.t. the test inputs, from a fitted factor (as gpr_predict).
+ * dgmu : d x m x nrhs, column-major, leading dimension d (a test point's gradient is
+ *        contiguous, as the point itself is in dXp);  dgmu[k, j, c] = d mu_c(xp_j) / d xp_kj
+ * dgvar: d x m (want_var != 0, else may be NULL): d sigma^2(xp_j) / d xp_kj of the DIAG variance
+ * dwork: optional n*m doubles (want_var; NULL: the context allocates)
+ * No counterpart in the reference.  With alpha = dwt and Q = K^{-1} K(x, xp) (the cross build and a
+ * solve from the factor, want_var only: GPR_PGRAD_SOLVE), one fused pass each, never
+ * materialising a dK matrix:
+ *   dgmu[k, j]  =      sum_p sum_i alpha_i (-W_p(xp_j, x_i)) dD_p/dxp_kj     (per column of dwt)
+ *   dgvar[k, j] = -2   sum_p sum_i Q_ij    (-W_p(xp_j, x_i)) dD_p/dxp_kj
+ * over the stationary parts p (the rules are in the opening comment).  Every kind, any d >= 1 and
+ * any number of parts (d <= 32 without a Periodic part: the test point and its d sums in
+ * registers; else 32 dimensions at a time, Periodic 16).
+ * ALWAYS the cross kernel: the gradients are those of the smooth function x* -> (mu, sigma^2), so
+ * dXp == dX gets NO same-object treatment here (unlike gpr_predict) -- the same-object eps is a
+ * point mass on the diagonal and has no derivative.  eps is taken only to build the description.
+ * The sum over i is cut into slabs of GPR_PGRAD_SLAB training points whose partial sums are added
+ * in a fixed order (no atomics): two calls on the same inputs agree bit for bit.  Asynchronous.
+ * Argument errors: GPR_E_ARG, the message names the argument, nothing is written. */
+int gpr_predict_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                     const double* dX, int n, const double* dU, int ldu, const double* dwt,
+                     int nrhs, const double* dXp, int m, int want_var, double eps,
+                     double* dgmu, double* dgvar, double* dwork);
 
 /* ---- a5/a6/a7 fused: update_cache!(::MllGradCache) = K, cholesky!, alpha, K^{-1} --------- */
 /* src/cost.jl:83-111 in one call: K into dK (upper -> U, lower keeps K), alpha = K^{-1} y
