@@ -160,7 +160,7 @@ struct KParBlock {
 enum TimingClass {
   TC_KBUILD = 0, TC_SYRK = 1, TC_PANEL = 2, TC_TRSM_GEMM = 3, TC_OTHER = 4, TC_GEMM_PIPE = 5,
   TC_DAG = 6, TC_DAG_SOLVE = 7, TC_PGRAD_MEAN = 8, TC_PGRAD_VAR = 9, TC_PGRAD_SOLVE = 10,
-  TC_N = 11
+  TC_APPEND_SOLVE = 11, TC_N = 12
 };
 
 struct TimedLaunch {
@@ -275,6 +275,8 @@ struct gpr_ctx {
   size_t panel_cap = 0;
   double* dtrsv = nullptr;      // single-launch triangular sweep hand-off vector (n x 2)
   size_t trsv_cap = 0;
+  double* dahand = nullptr;     // the append's skinny solve: hand-off blocks (128 x 16 per block)
+  size_t ahand_cap = 0;
   double* dxs = nullptr;        // per-part scaled training inputs  (nse x d x n)
   size_t xs_cap = 0;
   double* dxps = nullptr;       // per-part scaled second inputs    (nse x d x m)
@@ -335,6 +337,9 @@ struct gpr_ctx {
   int pgrad_solve = -1;         // GPR_PGRAD_SOLVE: Q = K^{-1} K(x, xp) of the variance gradient by
                                 // potrs_core's sweeps (0), by Z = U^{-T} and two MFMA products (1),
                                 // -1 auto (predict_grad.hip)
+  int append_sweep = -1;        // GPR_APPEND_SWEEP: V = U^{-T} K(x, x_new) of gpr_fit_append by the
+                                // single-launch skinny sweep (1, m <= 128), by trsm_ut_core (0),
+                                // -1 auto (append.hip)
 
   bool timing = false;
   std::vector<TimedLaunch> pending;
@@ -483,6 +488,11 @@ int launch_potrf_dag_padded(gpr_ctx* ctx, double* dA, int n, int lda, double* dB
 int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info,
                const RhsSpec* rhs = nullptr);
 int ensure_factor_inverses(gpr_ctx* ctx, const double* dU, int n, int ldu);
+// the diagonal-block kernels on their own (potrf.hip): factor the block at kglob of A in place
+// (inverse into winv; a failing pivot: kglob + its order in ctx->dinfo), and ctx->winv's slots
+// from block b0 on recomputed from the factor
+int diag_factor_block(gpr_ctx* ctx, double* A, int lda, int n, int kglob, double* winv);
+int diag_inverse_blocks(gpr_ctx* ctx, const double* dU, int ldu, int n, int b0);
 int trsm_ut_core(gpr_ctx* ctx, const double* dU, int n, int ldu, double* dB, int nrhs,
                  int ldb, double* norm_out, int lower_rhs);
 int kinv_from_z(gpr_ctx* ctx, const double* Z, int n, double* dKinv, int ldk);

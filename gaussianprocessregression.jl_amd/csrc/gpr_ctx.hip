@@ -250,6 +250,7 @@ const Knob kKnobs[] = {
     {"GPR_QUAD_SEQ", &gpr_ctx::quad_seq, nullptr},
     {"GPR_PGRAD_SLAB", &gpr_ctx::pgrad_slab, nullptr},
     {"GPR_PGRAD_SOLVE", &gpr_ctx::pgrad_solve, nullptr},
+    {"GPR_APPEND_SWEEP", &gpr_ctx::append_sweep, nullptr},
 };
 
 void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
@@ -372,6 +373,7 @@ int gpr_ctx_destroy(gpr_ctx_t ctx) {
   if (ctx->dbig) hipFree(ctx->dbig);
   if (ctx->dbig2) hipFree(ctx->dbig2);
   if (ctx->dtrsv) hipFree(ctx->dtrsv);
+  if (ctx->dahand) hipFree(ctx->dahand);
   if (ctx->dsqinv) hipFree(ctx->dsqinv);
   if (ctx->dpanel) hipFree(ctx->dpanel);
   if (ctx->dxs) hipFree(ctx->dxs);

@@ -34,6 +34,7 @@ extern "C" void gpr_debug_diag_stamps(unsigned long long* out) {
 #endif
 
 #include "diag_block.hpp"
+#include "sweep_handoff.hpp"
 
 namespace {
 
@@ -634,59 +635,7 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// SWEEP_SC1 (default): the hand-off vector is written and read ONLY with sc1 (L2-coherent,
-// write-through) accesses and the counter is an sc1 store polled by sc1 loads, each polling
-// wave loading only after its own poll matched -- MI355X_MICROARCH.md's first sc1 hand-off
-// row (hipMalloc memory, one workgroup per CU), which needs neither the producer's L2
-// write-back (release, 1.7-6.5 us) nor the consumer's L1 invalidate (acquire, 1.7-7 us) on
-// each of the 256 hops of a sweep.  SWEEP_SC1=0: plain accesses behind agent fences.
-#ifndef SWEEP_SC1
-#define SWEEP_SC1 1
-#endif
-__device__ __forceinline__ double hand_ld(const double* p) {
-#if SWEEP_SC1
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void hand_st(double* p, double v) {
-#if SWEEP_SC1
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *p = v;
-#endif
-}
-
-// Block until at least `need` blocks are published; `known` caches the last observed count.
-__device__ __forceinline__ void sweep_wait(int* sync, int need, int& known, int lane) {
-  if (known >= need) return;
-  int v = 0;
-  if (lane == 0) {
-    while ((v = __hip_atomic_load(&sync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < need)
-      __builtin_amdgcn_s_sleep(1);
-  }
-  known = __shfl(v, 0);
-#if SWEEP_SC1
-  // no instruction: keeps the compiler from hoisting the sc1 hand-off loads above the poll
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#else
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-
-__device__ __forceinline__ void sweep_publish(int* sync, int value) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave, before the barrier
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#if !SWEEP_SC1
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    __hip_atomic_store(&sync[1], value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
+// hand_ld / hand_st / sweep_wait / sweep_publish: sweep_handoff.hpp
 
 // Forward sweep U^T z = b: block b needs sum_{k<b} U[k-rows, b-cols]^T z_k, a column-dot per
 // b-column; each lane keeps partial dots over rows (2l, 2l+1) for its wave's 16 columns and
@@ -1091,6 +1040,21 @@ int rhs_panel_step(gpr_ctx* ctx, const double* dU, int n, int ldu, const RhsSpec
 }
 
 }  // namespace
+
+// ---- the diagonal-block kernels for append.hip (the launchers above are file-local) ----------
+// Factor the diagonal block at kglob of A (n x n) in place, its inverse into `winv`; a failing
+// pivot leaves kglob + its order in ctx->dinfo (cleared by the caller).
+int diag_factor_block(gpr_ctx* ctx, double* A, int lda, int n, int kglob, double* winv) {
+  return launch_diag(ctx, A, lda, n, kglob, winv, 1, 1);
+}
+// ctx->winv slots b0.. <- the inverses of the factor's diagonal blocks b0.. (n x n, block nb)
+int diag_inverse_blocks(gpr_ctx* ctx, const double* dU, int ldu, int n, int b0) {
+  const int nb = ctx->nb, nblk = (n + nb - 1) / nb;
+  if (b0 >= nblk) return 0;
+  const size_t o = (size_t)b0 * nb;
+  return launch_diag(ctx, const_cast<double*>(dU) + o + o * ldu, ldu, n - (int)o, 0,
+                     ctx->winv + (size_t)b0 * nb * nb, 0, nblk - b0);
+}
 
 // Debug timing of the chain kernels (tools/gemm_bench mode 6 only), averaged over the
 // diagonal blocks 0 .. reps-1 of a freshly assembled SPD matrix A (each factored once):

@@ -37,6 +37,7 @@ from .core import (
     log_loss_grad_,
     loss,
     loss_grad_,
+    append_,
     predict,
     predict_,
     predict_grad,

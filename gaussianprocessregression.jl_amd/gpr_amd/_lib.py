@@ -74,6 +74,7 @@ _SIGS = {
     "gpr_mll": (_i, [_p, _p, _i, _i, _p, _p, _dp]),
     "gpr_mll_grad": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _d, _i, _dp]),
     "gpr_fit": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _d, _p, _i, _p, _ip]),
+    "gpr_fit_append": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _i, _p, _i, _i, _d, _p, _i, _p, _p, _ip]),
     "gpr_predict": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _d, _p, _p,
                          _i, _p]),
     "gpr_predict_grad": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _d, _p, _p,

@@ -412,13 +412,25 @@ def islog(cost, md: GPRModel):
     return LogScale() if any(is_stationary(k) for k in md.covar.parts()) else NoLogScale()
 
 
-class MllLossCache:
-    """Device-resident MllLossCache(hp, kchol_base, alpha) (src/caches/cost.jl:6-19)."""
+def _cache_ld(md: "GPRModel", capacity: Optional[int]) -> int:
+    """Leading dimension of a cache's factor buffer: exactly n by default, `capacity` (>= n) to
+    leave room for append_ without a regrowth."""
+    if capacity is None:
+        return md.n
+    if int(capacity) < md.n:
+        raise ValueError(f"capacity {capacity} is smaller than the model's {md.n} points")
+    return int(capacity)
 
-    def __init__(self, md: GPRModel):
+
+class MllLossCache:
+    """Device-resident MllLossCache(hp, kchol_base, alpha) (src/caches/cost.jl:6-19).
+    ``capacity`` as for GPRPredictCache: room in kchol_base for append_."""
+
+    def __init__(self, md: GPRModel, capacity: Optional[int] = None):
         self.ctx = md.ctx
         self.hp = md.params.copy()
-        self.kchol_base = self.ctx.empty(md.n, md.n)  # column-major N x N
+        self.ld = _cache_ld(md, capacity)  # leading dimension of kchol_base (room for append_)
+        self.kchol_base = self.ctx.empty(self.ld, self.ld)  # column-major N x N
         self.alpha = self.ctx.empty(md.n)
         self.info = 0
 
@@ -429,8 +441,8 @@ class MllGradCache(MllLossCache):
     The reference keeps per-part kernel matrices and a dK buffer; the fused gradient
     recomputes K_p and dK in registers, so only U, alpha and K^{-1} are kept."""
 
-    def __init__(self, md: GPRModel):
-        super().__init__(md)
+    def __init__(self, md: GPRModel, capacity: Optional[int] = None):
+        super().__init__(md, capacity)
         self.Kinv = self.ctx.empty(md.n, md.n)
 
 
@@ -446,11 +458,11 @@ def update_cache_(tc: MllLossCache, hp, md: GPRModel, eps: float = EPS_DEFAULT):
     n = md.n
     if isinstance(tc, MllGradCache):  # K, U, alpha and K^{-1} in one call (src/cost.jl:83-111)
         rc = lib.gpr_fit_kinv(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), n, _ptr(y), 1, n, eps,
-                              _ptr(tc.kchol_base), n, _ptr(tc.alpha), _ptr(tc.Kinv), n,
+                              _ptr(tc.kchol_base), tc.ld, _ptr(tc.alpha), _ptr(tc.Kinv), n,
                               ctypes.byref(info))
     else:
         rc = lib.gpr_fit(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), n, _ptr(y), 1, n, eps,
-                         _ptr(tc.kchol_base), n, _ptr(tc.alpha), ctypes.byref(info))
+                         _ptr(tc.kchol_base), tc.ld, _ptr(tc.alpha), ctypes.byref(info))
     tc.info = info.value
     if info.value != 0:
         raise PosDefException(info.value)
@@ -460,7 +472,7 @@ def update_cache_(tc: MllLossCache, hp, md: GPRModel, eps: float = EPS_DEFAULT):
 def _mll_value(md: GPRModel, tc: MllLossCache) -> float:
     ctx = md.ctx
     out = ctypes.c_double(0.0)
-    ctx.check(lib.gpr_mll(ctx.h, _ptr(tc.kchol_base), md.n, md.n, _ptr(md.dsample()),
+    ctx.check(lib.gpr_mll(ctx.h, _ptr(tc.kchol_base), md.n, tc.ld, _ptr(md.dsample()),
                           _ptr(tc.alpha), ctypes.byref(out)), "gpr_mll")
     return out.value
 
@@ -478,7 +490,12 @@ def _mll_grad(md: GPRModel, tc: MllGradCache, eps=EPS_DEFAULT, log_scale=False) 
 
 def loss(cost, hp_or_md, md: Optional[GPRModel] = None, tc: Optional[MllLossCache] = None,
          eps: float = EPS_DEFAULT) -> float:
-    """loss(MLL, md) / loss(MLL, hp, md) / loss(MLL, hp, md, tc) (src/cost.jl:17-22,40-43)."""
+    """loss(MLL, md) / loss(MLL, hp, md) / loss(MLL, hp, md, tc) (src/cost.jl:17-22,40-43);
+    loss(MLL, md, tc) reads the value off a cache that is already up to date."""
+    if isinstance(md, MllLossCache):
+        # loss(MLL, md, tc): the value from an up-to-date cache (update_cache_ or append_ made
+        # it), nothing refitted
+        return _mll_value(hp_or_md, md)
     if md is None:
         md, hp = hp_or_md, hp_or_md.params
     else:
@@ -537,11 +554,14 @@ def log_loss_grad_(cost, F, G, log_hp, md: GPRModel, tc: MllGradCache, eps: floa
 class GPRPredictCache:
     """Device-resident GPRPredictCache(Kxx, wt, Kxp) (src/caches/predict.jl:3-31).
 
-    Kxx holds the factor U after update_cache_; Kxp is kept transposed (N x np)."""
+    Kxx holds the factor U after update_cache_; Kxp is kept transposed (N x np).  ``capacity``
+    (>= md.n) allocates Kxx as capacity x capacity, leading dimension ``ld``, so that append_ can
+    extend the factor inside it; the default is the exact n x n buffer, ld = n."""
 
-    def __init__(self, md: GPRModel, nxp: int = 0):
+    def __init__(self, md: GPRModel, nxp: int = 0, capacity: Optional[int] = None):
         self.ctx = md.ctx
-        self.Kxx = self.ctx.empty(md.n, md.n)
+        self.ld = _cache_ld(md, capacity)  # leading dimension of Kxx (room for append_)
+        self.Kxx = self.ctx.empty(self.ld, self.ld)
         ny = 1 if md.y.ndim == 1 else md.y.shape[1]
         self.wt = self.ctx.empty(ny, md.n) if md.y.ndim == 2 else self.ctx.empty(md.n)
         self.nrhs = ny
@@ -555,7 +575,8 @@ def _update_predict_cache(pc, md: GPRModel, eps=EPS_DEFAULT):
     hpa, hpp = _hp_arr(md.params)
     info = ctypes.c_int(0)
     ctx.check(lib.gpr_fit(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(md.dy()), pc.nrhs,
-                          md.n, eps, _ptr(pc.Kxx), md.n, _ptr(pc.wt), ctypes.byref(info)),
+                          md.n, eps, _ptr(pc.Kxx), getattr(pc, "ld", md.n), _ptr(pc.wt),
+                          ctypes.byref(info)),
               "gpr_fit")
     if info.value != 0:
         raise PosDefException(info.value)
@@ -585,7 +606,7 @@ def predict_(mu: Optional[torch.Tensor], Sigma: Optional[torch.Tensor], md: GPRM
     mode = (_lib.GPR_PREDICT_MEAN if mean_only else
             _lib.GPR_PREDICT_DIAG if diagonal_var else _lib.GPR_PREDICT_FULL)
     ldv = m
-    ctx.check(lib.gpr_predict(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(pc.Kxx), md.n,
+    ctx.check(lib.gpr_predict(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(pc.Kxx), pc.ld,
                               _ptr(pc.wt), pc.nrhs, _ptr(dxp), m, mode, eps, _ptr(mu), _ptr(Sigma),
                               ldv, _ptr(pc.Kxp)), "gpr_predict")
 
@@ -629,7 +650,7 @@ def _fit_predict(md: GPRModel, dxp, m: int, pc: GPRPredictCache, mu, Sigma, diag
     mode = _lib.GPR_PREDICT_DIAG if diagonal_var else _lib.GPR_PREDICT_FULL
     info = ctypes.c_int(0)
     rc = lib.gpr_fit_predict(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(md.dy()),
-                             pc.nrhs, md.n, eps, _ptr(pc.Kxx), md.n, _ptr(pc.wt), _ptr(dxp), m,
+                             pc.nrhs, md.n, eps, _ptr(pc.Kxx), pc.ld, _ptr(pc.wt), _ptr(dxp), m,
                              mode, _ptr(mu), _ptr(Sigma), m, None, ctypes.byref(info))
     if info.value != 0:
         raise PosDefException(info.value)
@@ -781,7 +802,7 @@ def predict_grad_(dmu: torch.Tensor, dvar: Optional[torch.Tensor], md: GPRModel,
     if dvar is not None and pc.Kxp.numel() < m * md.n:
         pc.Kxp = ctx.empty(m, md.n)
     ctx.check(lib.gpr_predict_grad(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(pc.Kxx),
-                                   md.n, _ptr(pc.wt), pc.nrhs, _ptr(dxp), m,
+                                   pc.ld, _ptr(pc.wt), pc.nrhs, _ptr(dxp), m,
                                    0 if dvar is None else 1, eps, _ptr(dmu), _ptr(dvar),
                                    _ptr(pc.Kxp) if dvar is not None else None), "gpr_predict_grad")
 
@@ -802,6 +823,93 @@ def predict_grad(md: GPRModel, xp, var: bool = True, eps: float = EPS_DEFAULT):
     gm = dmu.cpu().numpy()
     gm = gm.transpose(0, 2, 1).copy() if gm.ndim == 3 else gm.T.copy()
     return gm, (ctx.host(dvar) if var else None)
+
+
+def _grown_ld(cap: int, need: int) -> int:
+    """Leading dimension after a regrowth: max(need, 1.125 cap) rounded up to 128."""
+    return -(-max(int(need), (9 * int(cap) + 7) // 8) // 128) * 128
+
+
+def append_(pc, md: GPRModel, x_new, y_new, eps: float = EPS_DEFAULT):
+    """Condition the model and its cache on new observations in place, without refactoring:
+    gpr_fit_append adds the m new columns of the factor (O(n^2 m)) and updates K^{-1} y by the
+    block formula.  x_new: d x m (length m when d = 1); y_new: m, or m x ny like md.y.
+
+    pc is an updated GPRPredictCache (Kxx, wt) or MllLossCache (kchol_base, alpha; then
+    loss-style calls on (md, pc) see the extended model with no refit).  An MllGradCache is
+    refused: its K^{-1} is not updated.  md.x / md.y and their device copies are extended by
+    concatenation (md.x becomes a new array, and stays the object `predict(md, md.x)` recognises).
+
+    A cache built with ``capacity >= n + m`` is extended inside its buffer.  Otherwise the buffer
+    grows first, geometrically: the new leading dimension is max(n + m, 1.125 capacity) rounded up
+    to a multiple of 128, the n x n block is copied across by one strided device copy and the
+    context is told to forget the old factor.
+
+    Raises PosDefException(info) when the extended matrix is not positive definite (info as
+    dpotrf on the whole matrix) and leaves md and pc exactly as they were (a buffer that grew keeps
+    its new size); ValueError on a shape mismatch and TypeError for a Cmap, before anything is
+    touched."""
+    if isinstance(x_new, Cmap):
+        raise TypeError("append_ takes the new points as a d x m array, not a Cmap")
+    if isinstance(pc, MllGradCache):
+        raise TypeError("append_ does not update an MllGradCache (its K^{-1} is not extended): "
+                        "refit it, or keep an MllLossCache")
+    is_mll = isinstance(pc, MllLossCache)
+    if not is_mll and not isinstance(pc, GPRPredictCache):
+        raise TypeError(f"append_ needs a GPRPredictCache or an MllLossCache, not {type(pc)!r}")
+    xn = np.asarray(x_new, dtype=np.float64)
+    if xn.ndim == 0:
+        xn = xn[None]
+    if xn.ndim == 1:
+        xn = xn[None, :] if md.d == 1 else xn[:, None]
+    if xn.ndim != 2 or xn.shape[0] != md.d:
+        raise ValueError(f"x_new has {xn.shape[0] if xn.ndim == 2 else '?'} rows, the model's "
+                         f"inputs have dimension {md.d}")
+    m = xn.shape[1]
+    if m < 1:
+        raise ValueError("x_new holds no point")
+    yn = np.asarray(y_new, dtype=np.float64)
+    if yn.ndim == 0 and md.y.ndim == 1:
+        yn = yn[None]
+    if yn.ndim != md.y.ndim or yn.shape[0] != m or (yn.ndim == 2 and yn.shape[1] != md.y.shape[1]):
+        raise ValueError(f"y_new of shape {yn.shape} does not match {m} new points and the "
+                         f"model's y of shape {md.y.shape}")
+    ctx = md.ctx
+    n0, N = md.n, md.n + m
+    buf_name, wt_name = ("kchol_base", "alpha") if is_mll else ("Kxx", "wt")
+    buf, wt0 = getattr(pc, buf_name), getattr(pc, wt_name)
+    if N > pc.ld:
+        ld = _grown_ld(pc.ld, N)
+        new = ctx.empty(ld, ld)
+        with torch.cuda.stream(ctx.stream):
+            new[:n0, :n0].copy_(buf[:n0, :n0])
+        ctx.check(lib.gpr_forget_factor(ctx.h), "gpr_forget_factor")
+        setattr(pc, buf_name, new)
+        pc.ld = ld
+        buf = new
+    with torch.cuda.stream(ctx.stream):
+        dx = torch.cat([md.dx(), ctx.colmajor(xn)], dim=0).contiguous()
+        dy = torch.cat([md.dy(), ctx.colmajor(yn)], dim=-1).contiguous()
+    if is_mll:  # the training sample's column, as update_cache_ fits it
+        nrhs, ysrc = 1, (dy if dy.ndim == 1 else dy[md.train_axis - 1])
+    else:
+        nrhs, ysrc = pc.nrhs, dy
+    wt = ctx.empty(*wt0.shape[:-1], N)
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(pc.hp if is_mll else md.params)
+    info = ctypes.c_int(0)
+    rc = lib.gpr_fit_append(ctx.h, kinds, nk, hpp, md.d, _ptr(dx), n0, m, _ptr(ysrc), nrhs, N, eps,
+                            _ptr(buf), pc.ld, _ptr(wt0), _ptr(wt), ctypes.byref(info))
+    if info.value != 0:
+        if is_mll:
+            pc.info = info.value
+        raise PosDefException(info.value)
+    ctx.check(rc, "gpr_fit_append")
+    x_all = np.concatenate([md.x, xn], axis=1)
+    md.x = md._x_obj = x_all
+    md.y = np.concatenate([md.y, yn], axis=0)
+    md._dx, md._dy = dx, dy
+    setattr(pc, wt_name, wt)
 
 
 def similar(md: GPRModel, hp, x, y) -> GPRModel:

@@ -135,7 +135,9 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *        launches (with any right-hand sides they solve), 7 solve-only tile-DAG launches
  *        (U^{-T} B from a finished factor: C5's variance rows, POTRI's Z), 8 / 9 the mean /
  *        variance pass of gpr_predict_grad (its kernels and their fixed-order sum), 10 the solve
- *        that makes its Q (call-level: the launches inside it also count in their own classes).
+ *        that makes its Q (call-level: the launches inside it also count in their own classes),
+ *        11 the append's skinny solve (V = U^{-T} K(x, x_new) of gpr_fit_append, whichever route
+ *        takes it; call-level too; the flops slot carries n0^2 m).
  *        Returns accumulated ms, launch count, flops (bytes for class 0). */
 /* Knobs: the library's run-time switches.  Each is a GPR_* environment variable read ONCE,
  * when a context is created, and can be changed on a live context with gpr_set_knob (values
@@ -190,6 +192,11 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         MFMA products, Q = Z^T (U^{-T} K(x, xp)) (1: n^2 + n m doubles of
  *                         workspace); -1 auto: the products for m > max(16, n / 512).  Measured at
  *                         n = 32768, m = 8192: 26.7 s by the sweeps, 535 ms by the products
+ *   GPR_APPEND_SWEEP  -1  gpr_fit_append: V = U^{-T} K(x, x_new) by the single-launch skinny sweep
+ *                         (1: for m <= 128 with the default 128 block, one pass over U per 16
+ *                         columns) or by the GEMM-based solve of gpr_trsm_upper_trans (0); -1 auto:
+ *                         the sweep for m <= 48.  Measured at n0 = 32768 - m, sweep vs the GEMM
+ *                         route: m = 1 1.78 vs 10.4 ms, 16 2.36 vs 9.0, 48 7.05 vs 9.1, 64 9.39 vs 9.18
  * A gpr_mgpu handle has knobs of its own, read from the environment once at gpr_mgpu_create
  * and changed with gpr_mgpu_set_knob / gpr_mgpu_get_knob (below):
  *   GPR_MGPU_STREAM   -1  1: stream U out during device 0's fit; 0: after it (-1 auto: only
@@ -285,6 +292,38 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
 int gpr_fit(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
             const double* dX, int n, const double* dy, int nrhs, int ldy, double eps,
             double* dK, int ldk, double* dalpha, int* info);
+
+/* Condition a fitted model on m more observations without refactoring it (no counterpart in the
+ * reference, whose only route is update_cache! on all points).  dX: d x (n0 + m), the m new points
+ * its last m columns; dy: (n0 + m) x nrhs (ldy).  dK (ldk >= n0 + m): on entry its leading n0 x n0
+ * is what gpr_fit left for the first n0 points under the same kinds, hp and eps (U in the upper
+ * triangle, K strictly below).  dalpha0: the old K^{-1} y, n0 x nrhs with leading dimension n0,
+ * read only; dalpha: (n0 + m) x nrhs with leading dimension n0 + m, receives the new K^{-1} y and
+ * must be distinct from dalpha0.
+ * On return with *info = 0 the leading (n0 + m) x (n0 + m) of dK is what gpr_fit on all n0 + m
+ * points would have left (within rounding): the factor in the upper triangle, K in the GPR_SELF
+ * form strictly below (the new diagonal block with eps per stationary part and the first
+ * WhiteNoise's sigma_n^2, the cross block the plain cross kernel); the old n0 x n0 block is not
+ * rewritten.  With B = K(x, x_new), V = U^{-T} B, S = K_new - V^T V = R^T R the new factor is
+ * [U V; 0 R], and alpha by the block formula: alpha_tail = S^{-1} (y_new - B^T alpha0),
+ * alpha_head = alpha0 - U^{-1} (V alpha_tail) -- O(n0^2 m) work.  V for m <= 128 by one
+ * persistent launch per 16 columns that reads the upper triangle of U once (GPR_APPEND_SWEEP),
+ * wider appends by the GEMM-based solve of gpr_trsm_upper_trans; V^T V summed over slabs of n0 in
+ * a fixed order (no atomics): two calls on the same inputs agree bit for bit.
+ * The context's factor cache is left valid for the extended factor (the block inverses from block
+ * n0 / 128 on are recomputed; a cached factor other than this buffer is established first, as any
+ * solve does): gpr_predict, gpr_predict_grad, gpr_mll, gpr_potrs_upper, gpr_mvn_sample on
+ * (dK, n0 + m, ldk) follow with no gpr_forget_factor.
+ * A Schur complement that is not positive definite: *info = n0 + j (j the order of its failing
+ * minor -- what dpotrf on the whole matrix gives), also the return value; the leading n0 x n0 of dK
+ * and dalpha0 are untouched, the old model stays usable.  GPR_E_ARG for m < 1, n0 < 1,
+ * ldk < n0 + m, ldy < n0 + m, nrhs < 1, a NULL pointer or dalpha == dalpha0: the message names the
+ * argument, nothing is written.  Every kind, any d, any number of parts, any n0 and m >= 1.
+ * Synchronises for info, as gpr_fit. */
+int gpr_fit_append(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                   const double* dX, int n0, int m, const double* dy, int nrhs, int ldy,
+                   double eps, double* dK, int ldk, const double* dalpha0, double* dalpha,
+                   int* info);
 
 /* ---- a10/a11: posterior ------------------------------------------------------------ */
 /* Posterior at m test points from a fitted factor (dU, dwt = K^{-1} y with nrhs cols).
