@@ -151,7 +151,10 @@ __device__ __forceinline__ double sqdist(const double* xr, const double* __restr
 // (x !== xp): rows from xs, columns from xps, no eps, no noise.
 // (One body rather than a shared device function: with the 16 sums handed to a helper by
 // reference the compiler kept them twice, 32 more VGPRs in every instantiation.)
-template <int D, bool SYM, bool MIX>
+// PROD: the description has a product term -- a part's value is multiplied into the running
+// product tm of its term, and the term is added (with eps once, on i == j) when a part closes it
+// (kp.tend, the device table: any number of parts).
+template <int D, bool SYM, bool MIX, bool PROD = false>
 __global__ __launch_bounds__(256) void kmat_cols_kernel(KParams kp, const double* __restrict__ xs,
                                                         int n, const double* __restrict__ xps,
                                                         int mp, double* __restrict__ K, size_t ldk,
@@ -176,6 +179,8 @@ __global__ __launch_bounds__(256) void kmat_cols_kernel(KParams kp, const double
   double vals[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) vals[c] = 0.0;
+  double tm[PROD ? 16 : 1];  // the open term's running product
+  bool opens = true, first = true;  // part p opens a term; no term has been added yet
   // parts outermost so only one part's row features live in registers; the per-element
   // accumulation order stays part 1, part 2, ... as in src/compose_covar.jl:52-56.
   for (int p = 0; p < kp.nse; ++p) {
@@ -187,6 +192,7 @@ __global__ __launch_bounds__(256) void kmat_cols_kernel(KParams kp, const double
     }
     const double s2 = kp.sig[p] * kp.sig[p];  // (any number of parts: the device table)
     const int prof = MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0;
+    const bool closes = PROD ? __builtin_amdgcn_readfirstlane((int)kp.tend[p]) != 0 : true;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const int j = j0 + wv + 4 * c;  // wave-uniform column
@@ -199,9 +205,22 @@ __global__ __launch_bounds__(256) void kmat_cols_kernel(KParams kp, const double
           dist = sqdist<0>(xrow, xc, d);
         }
         double t = MIX ? kprof_neg(prof, s2, dist) : s2 * kexp_neg(dist);
-        if (SYM && i == j) t += kp.eps;
-        vals[c] = (p == 0) ? t : vals[c] + t;
+        if constexpr (PROD) {
+          tm[c] = opens ? t : tm[c] * t;
+          if (closes) {
+            t = tm[c];
+            if (SYM && i == j) t += kp.eps;
+            vals[c] = first ? t : vals[c] + t;
+          }
+        } else {
+          if (SYM && i == j) t += kp.eps;
+          vals[c] = (p == 0) ? t : vals[c] + t;
+        }
       }
+    }
+    if (PROD) {
+      if (closes) first = false;
+      opens = closes;
     }
   }
   if (SYM && kp.has_noise) {
@@ -236,8 +255,11 @@ __global__ __launch_bounds__(256) void kmat_cols_kernel(KParams kp, const double
 // Periodic part (xs: the embedded points, de wide): which = k+1 <= d ->
 // -2 l_k K (2 sin(pi r_k / p_k))^2, which = d+k+1 -> (4 pi l_k^2 / p_k^2) K r_k sin(2 pi r_k / p_k),
 // r = x_a - x_b on raw x, K without eps (eps meets r = 0 only).
+// Part p is a factor of the term of parts [t0, t1]: C = the product of the other factors' values
+// (formed as a product, never as T / K_p, which underflows); which = 0 -> (2/|sigma|) (K_p C + eps
+// on the diagonal), else the formulas above with W C for W.  A term of one factor: C = 1 exactly.
 __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
-                             const double* __restrict__ xs, int n, int p, int which,
+                             const double* __restrict__ xs, int n, int p, int t0, int t1, int which,
                              double* __restrict__ DK, size_t ld) {
   const int d = kp.dx, de = kp.de;
   const bool per = kp.per && kp.per[p] != 0.0;
@@ -253,6 +275,20 @@ __global__ void kgrad_kernel(KParams kp, const double* __restrict__ X,
     }
     double W;
     double Kp = kprof_exact_w((int)kp.pf[p], kp.sig[p] * kp.sig[p], s, &W);
+    for (int g = t0; g <= t1; ++g) {
+      if (g == p) continue;
+      const double* ga = xs + ((size_t)g * n + a) * de;
+      const double* gb = xs + ((size_t)g * n + b) * de;
+      double sg = 0.0;
+      for (int k = 0; k < de; ++k) {
+        const double q = ga[k] - gb[k];
+        sg = fma(q, q, sg);
+      }
+      double Wg;
+      const double C = kprof_exact_w((int)kp.pf[g], kp.sig[g] * kp.sig[g], sg, &Wg);
+      Kp *= C;
+      W *= C;
+    }
     if (a == b) Kp += kp.eps;
     double v;
     if (which == 0) {
@@ -339,7 +375,10 @@ constexpr int KT_LDS = KT * (KT + 1);  // doubles; also holds the 64 x D column 
 // (only these 1/nt of the tiles pay the index compares).  tabs = nse tables of 256 doubles.
 // MIX: some part is a Matern part -- each part's element loop is entered through one scalar
 // branch on its profile (kprof_dispatch); MIX = false compiles the SquaredExp loop alone.
-template <int D, bool DIAG, bool MIX>
+// PROD: some term is a product -- a part's value goes into its term's running product tm, and
+// the term into the tile (eps once per term) when the part closes it (kp.tendm, by value);
+// PROD = false compiles the sum of parts alone.
+template <int D, bool DIAG, bool MIX, bool PROD = false>
 __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const double* __restrict__ xs,
                                                   int n, const double* __restrict__ xcs, int m,
                                                   int i0, int j0, double* lds, const double* tabs,
@@ -349,7 +388,10 @@ __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const doubl
   const int ia = min(i0 + 2 * l32, n - 1), ib = min(i0 + 2 * l32 + 1, n - 1);
 #pragma unroll
   for (int c = 0; c < 8; ++c) v[c][0] = v[c][1] = 0.0;
+  double tm[PROD ? 8 : 1][2];
   for (int p = 0; p < kp.nse; ++p) {
+    const bool opens = !PROD || p == 0 || ((kp.tendm >> (p - 1)) & 1);
+    const bool closes = !PROD || ((kp.tendm >> p) & 1);
     const double* xp_rows = xs + (size_t)p * n * D;
     const double* xp_cols = xcs + (size_t)p * m * D;
     // all global loads of this part first (row features + this thread's column-point share)
@@ -393,6 +435,11 @@ __device__ __forceinline__ void kmat_tile_compute(const KParams& kp, const doubl
       for (int c = 0; c < KB_CG; ++c) {
         constexpr int PF = decltype(pf)::value;
         double t0 = kprof_s2<PF>(d0[c], ts), t1 = kprof_s2<PF>(d1[c], ts);
+        if constexpr (PROD) {
+          t0 = tm[cb + c][0] = opens ? t0 : tm[cb + c][0] * t0;
+          t1 = tm[cb + c][1] = opens ? t1 : tm[cb + c][1] * t1;
+          if (!closes) continue;
+        }
         if (DIAG) {
           const int j = j0 + cg + 8 * (cb + c), i = i0 + 2 * l32;
           if (i == j) t0 += kp.eps;
@@ -448,7 +495,7 @@ __device__ __forceinline__ void store_pair(double* K, size_t idx, bool ok0, bool
 // their launch bounds, and their allocation follows the source closely: the direct store moved
 // into a helper shared with the Gram tile kernels changed spills in ten instantiations, by up
 // to 29 VGPRs where the helper took the register tile through a lambda.)
-template <int D, bool MIX>
+template <int D, bool MIX, bool PROD = false>
 __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams kp, const double* __restrict__ xs,
                                                         int n, double* __restrict__ K, size_t ldk,
                                                         int ntiles) {
@@ -466,9 +513,9 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams
     const int i0 = bi * KT, j0 = bj * KT;
     double v[8][2];
     if (bi == bj)
-      kmat_tile_compute<D, true, MIX>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
+      kmat_tile_compute<D, true, MIX, PROD>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
     else
-      kmat_tile_compute<D, false, MIX>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
+      kmat_tile_compute<D, false, MIX, PROD>(kp, xs, n, xs, n, i0, j0, lds, tabs, v);
     const int i = i0 + 2 * l32;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -496,7 +543,7 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_sym2_kernel(KParams
   }
 }
 
-template <int D, bool MIX>
+template <int D, bool MIX, bool PROD = false>
 __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_cross2_kernel(KParams kp, const double* __restrict__ xs,
                                                           int n, const double* __restrict__ xps,
                                                           int m, double* __restrict__ K,
@@ -511,7 +558,7 @@ __global__ __launch_bounds__(256, GPR_KBUILD_MINB) void kmat_cross2_kernel(KPara
     const int bi = bid % ntile_i, bj = bid / ntile_i;
     const int i0 = bi * KT, j0 = bj * KT;
     double v[8][2];
-    kmat_tile_compute<D, false, MIX>(kp, xs, n, xps, m, i0, j0, lds, tabs, v);
+    kmat_tile_compute<D, false, MIX, PROD>(kp, xs, n, xps, m, i0, j0, lds, tabs, v);
     const int i = i0 + 2 * l32;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -527,18 +574,18 @@ template <int D>
 void launch_sym(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, double* K, int ldk) {
   const int nt = (n + KT - 1) / KT;
   const long long nblk = (long long)nt * (nt + 1) / 2;
-  kmix_dispatch(kp.mix, [&](auto mix) {
-    constexpr bool MIX = decltype(mix)::value;
+  kmixprod_dispatch(kp.mix, kp.prod, [&](auto mix, auto prod) {
+    constexpr bool MIX = decltype(mix)::value, PROD = decltype(prod)::value;
     if constexpr (D > 0) {
       if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {
         const int grid = (int)std::min<long long>(nblk, kbuild_grid());
         const size_t lds_bytes = sizeof(double) * (KT_LDS + 256 * kp.nse);
-        kmat_sym2_kernel<D, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
+        kmat_sym2_kernel<D, MIX, PROD><<<grid, 256, lds_bytes, ctx->stream>>>(kp, xs, n, K, (size_t)ldk, (int)nblk);
         return;
       }
     }
-    kmat_cols_kernel<D, true, MIX><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, nullptr, 0, K,
-                                                                           (size_t)ldk, 0);
+    kmat_cols_kernel<D, true, MIX, PROD><<<(unsigned)nblk, 256, 0, ctx->stream>>>(kp, xs, n, nullptr, 0, K,
+                                                                                 (size_t)ldk, 0);
   });
 }
 
@@ -547,18 +594,18 @@ void launch_cross(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, cons
                   int m, double* K, int ldk) {
   const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
   const unsigned nblk = (unsigned)((long long)nti * ntj);
-  kmix_dispatch(kp.mix, [&](auto mix) {
-    constexpr bool MIX = decltype(mix)::value;
+  kmixprod_dispatch(kp.mix, kp.prod, [&](auto mix, auto prod) {
+    constexpr bool MIX = decltype(mix)::value, PROD = decltype(prod)::value;
     if constexpr (D > 0) {
       if (vec_store_ok(K, ldk) && kp.nse <= KMAXP) {
         const int grid = (int)std::min<long long>(nblk, kbuild_grid());
         const size_t lds_bytes = sizeof(double) * (KT * D + 256 * kp.nse);
-        kmat_cross2_kernel<D, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
+        kmat_cross2_kernel<D, MIX, PROD><<<grid, 256, lds_bytes, ctx->stream>>>(
             kp, xs, n, xps, m, K, (size_t)ldk, nti, (int)nblk);
         return;
       }
     }
-    kmat_cols_kernel<D, false, MIX><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
+    kmat_cols_kernel<D, false, MIX, PROD><<<nblk, 256, 0, ctx->stream>>>(kp, xs, n, xps, m, K, (size_t)ldk, nti);
   });
 }
 
@@ -646,17 +693,27 @@ __global__ void gram_prep_kernel(const double* __restrict__ xs, int n, int d, in
 //    operands).  96 operand / accumulator registers whatever d is.
 // DIAG: a diagonal tile of the symmetric K -- D = 0 exactly and eps per part on i == j,
 // sigma_n^2 after the parts.
+// PROD: some term is a product -- a part's value is multiplied into its term's running product,
+// and the term goes into v (eps once per term) when the part closes it (kp.tendm); PROD = false
+// compiles the sum of parts alone.  The running products live in tmw, the caller's tile staging
+// buffer (idle while a tile is computed): 16 slots per thread, tmw[16][256], each read and
+// written by its own thread only -- held in registers they cost 32 VGPRs and spilled (the full K
+// of SE*PER+WN measured 1.83 x SE+PER+WN that way).  The caller puts a barrier between the last
+// read of the staging buffer and this call.
 constexpr int GR_CH = 4;  // k-steps per chunk
-template <int SC, bool DIAG, bool MIX>
+template <int SC, bool DIAG, bool MIX, bool PROD = false>
 __device__ __forceinline__ void gram_tile(const KParams& kp, int S, const double* __restrict__ gA,
                                           const double* __restrict__ gB, const double* __restrict__ nA,
                                           const double* __restrict__ nB, int nblkA, int nblkB,
-                                          int i0, int j0, const double* tabs, gd4 (&v)[2][2]) {
+                                          int i0, int j0, const double* tabs, gd4 (&v)[2][2],
+                                          double* tmw = nullptr) {
   constexpr int NOP = SC > 0 ? SC : GR_CH;  // k-steps of operands held per 16-block
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wr = w & 1, wc = w >> 1;
   const int ba = (i0 >> 4) + 2 * wr, bb = (j0 >> 4) + 2 * wc;  // first 16-blocks
   for (int p = 0; p < kp.nse; ++p) {
+    const bool opens = !PROD || p == 0 || ((kp.tendm >> (p - 1)) & 1);
+    const bool closes = !PROD || ((kp.tendm >> p) & 1);
     const double* Ap = gA + ((size_t)p * nblkA + ba) * S * 64 + lane;
     const double* Bp = gB + ((size_t)p * nblkB + bb) * S * 64 + lane;
     const double* nAp = nA + (size_t)p * nblkA * 16 + ba * 16 + (lane >> 4);
@@ -744,8 +801,19 @@ __device__ __forceinline__ void gram_tile(const KParams& kp, int S, const double
             if (on_diag) x = 0.0;
           }
           double t = kprof_s2<decltype(pf)::value>(-x, ts);
-          if (DIAG && on_diag) t += kp.eps;
-          v[rb][cb][q] += t;
+          if constexpr (PROD) {
+            double* slot = tmw + ((rb * 2 + cb) * 4 + q) * 256 + threadIdx.x;
+            if (!opens) t *= *slot;
+            if (closes) {
+              if (DIAG && on_diag) t += kp.eps;
+              v[rb][cb][q] += t;
+            } else {
+              *slot = t;
+            }
+          } else {
+            if (DIAG && on_diag) t += kp.eps;
+            v[rb][cb][q] += t;
+          }
           if ((q + 1) % GRAM_EXPG == 0) __builtin_amdgcn_sched_barrier(0);
         }
     });
@@ -864,7 +932,7 @@ __device__ __forceinline__ void tile_store_mirror(const double* T, double* __res
 // (3 or 4 workgroups per CU); SC = 0: S at run time, 2 workgroups per CU, and with
 // ACC the tile adds to the K already stored.  Srt is read only by the SC = 0 instances (the others
 // take and ignore it, so that one launch line serves both).
-template <int SC, bool ACC, bool MIX>
+template <int SC, bool ACC, bool MIX, bool PROD = false>
 __global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_symg_kernel(
     KParams kp, int Srt, const double* __restrict__ gA, const double* __restrict__ gB,
     const double* __restrict__ nrm, int nblk, int n, double* __restrict__ K, size_t ldk,
@@ -881,10 +949,11 @@ __global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_symg_ker
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
     gram_tile_init<ACC>(K, ldk, i0, j0, n, n, T, v);
+    if constexpr (PROD) __syncthreads();  // T is read no more: it holds the running products now
     if (bi == bj)
-      gram_tile<SC, true, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile<SC, true, MIX, PROD>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v, T);
     else
-      gram_tile<SC, false, MIX>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v);
+      gram_tile<SC, false, MIX, PROD>(kp, S, gA, gB, nrm, nrm, nblk, nblk, i0, j0, tabs, v, T);
     __syncthreads();  // previous tile's LDS reads are done
     gram_to_lds(v, T);
     __syncthreads();
@@ -897,7 +966,7 @@ __global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_symg_ker
   }
 }
 
-template <int SC, bool ACC, bool MIX>
+template <int SC, bool ACC, bool MIX, bool PROD = false>
 __global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_crossg_kernel(
     KParams kp, int Srt, const double* __restrict__ gA, const double* __restrict__ gB,
     const double* __restrict__ nrmA, const double* __restrict__ nrmB, int nblkA, int nblkB, int n,
@@ -914,7 +983,8 @@ __global__ __launch_bounds__(256, SC > 0 ? (MIX ? 3 : 4) : 2) void kmat_crossg_k
     const int i0 = bi * KT, j0 = bj * KT;
     gd4 v[2][2];
     gram_tile_init<ACC>(K, ldk, i0, j0, n, m, T, v);
-    gram_tile<SC, false, MIX>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v);
+    if constexpr (PROD) __syncthreads();  // T is read no more: it holds the running products now
+    gram_tile<SC, false, MIX, PROD>(kp, S, gA, gB, nrmA, nrmB, nblkA, nblkB, i0, j0, tabs, v, T);
     __syncthreads();
     gram_to_lds(v, T);
     __syncthreads();
@@ -959,7 +1029,8 @@ __host__ __device__ inline int kup_rows(int j0, int n) { return min(n, 128 * (j0
 // and eps per part on i == j, sigma_n^2 after the parts); EDGE: rows past r1 / columns past n
 // masked.  Interior units store unconditionally, so the compiler counts the stores and the next
 // unit's prefetched operands are waited for with vmcnt(stores), not vmcnt(0).
-template <int S, int NSE, bool DIAG, bool EDGE, bool CLAMP>
+// PROD (NSE = 2): the two parts are the factors of one term -- multiplied, eps once.
+template <int S, int NSE, bool DIAG, bool EDGE, bool CLAMP, bool PROD = false>
 __device__ __forceinline__ void kup_unit(const KParams& kp, const double (&ca)[NSE][KU_CB][S],
                                          const double* cn, const double (&ra)[NSE][2][S],
                                          const double (&rn)[NSE][2], const double* tabs,
@@ -1006,10 +1077,16 @@ __device__ __forceinline__ void kup_unit(const KParams& kp, const double (&ca)[N
           if (on) x = 0.0;
         }
         e[q] = CLAMP ? kexp_s2(-x, ts) : kexp_s2_nc(-x, ts);
-        if (DIAG && on) e[q] += kp.eps;
+        if (!PROD && DIAG && on) e[q] += kp.eps;
       }
 #pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = p == 0 ? e[q] : v[q] + e[q];
+      for (int q = 0; q < 4; ++q) v[q] = p == 0 ? e[q] : PROD ? v[q] * e[q] : v[q] + e[q];
+      if constexpr (PROD && DIAG) {
+        if (p == NSE - 1)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (i0 + 16 * rb + (lane & 15) == j0 + 16 * cb + (lane >> 4) + 4 * q) v[q] += kp.eps;
+      }
       asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
     }
 #pragma unroll
@@ -1087,7 +1164,7 @@ __device__ __forceinline__ void kup_item_cols(const double (&ca)[1][KU_CB][S], c
   }
 }
 
-template <int S, int NSE>
+template <int S, int NSE, bool PROD = false>
 __global__ __launch_bounds__(256, KU_MINB) void kmat_symu_kernel(KParams kp, const double* __restrict__ gA,
                                                         const double* __restrict__ gB,
                                                         const double* __restrict__ nrm, int nblk,
@@ -1171,13 +1248,13 @@ __global__ __launch_bounds__(256, KU_MINB) void kmat_symu_kernel(KParams kp, con
       const bool clamp = __ballot(rbig) != 0;
       // (wave-uniform branches) the diagonal unit, ragged edges, the interior
       if (j0 >= i0 && j0 < i0 + KU_H)  // (the unit holds diagonal elements)
-        kup_unit<S, NSE, true, true, true>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
+        kup_unit<S, NSE, true, true, true, PROD>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
       else if (edge_cols || i0 + KU_H > r1)
-        kup_unit<S, NSE, false, true, true>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
+        kup_unit<S, NSE, false, true, true, PROD>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
       else if (clamp)
-        kup_unit<S, NSE, false, false, true>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
+        kup_unit<S, NSE, false, false, true, PROD>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
       else
-        kup_unit<S, NSE, false, false, false>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
+        kup_unit<S, NSE, false, false, false, PROD>(kp, ca, cn, ra, rn, tabs, K, ldk, i0, j0, r1, n, voff);
 #pragma unroll
       for (int p = 0; p < NSE; ++p)
 #pragma unroll
@@ -1243,7 +1320,8 @@ int gram_prepare(gpr_ctx* ctx, const KParams& kp, int S, const double* xs, int n
 // SC > 0: the tile kernels compiled for SC k-steps; SC = 0: the run-time-S ones (any d), which
 // with ACC add their parts to the K already stored (launch_gram_groups).  SE-only descriptions
 // (and SE-only groups of a mixed one) launch the MIX = false instantiations; a group with another
-// profile the MIX ones (one scalar branch per part).
+// profile the MIX ones (one scalar branch per part); one with a product term the PROD ones, MIX
+// by its profiles as before (SE * PER launches MIX = false, at the SE kernels' occupancy).
 template <int SC, bool ACC = false>
 int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const double* xps,
                 int m, int same, double* K, int ldk) {
@@ -1255,13 +1333,13 @@ int launch_gram(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, const 
   const int nti = (n + KT - 1) / KT, ntj = (m + KT - 1) / KT;
   const long long nblk = same ? (long long)nti * (nti + 1) / 2 : (long long)nti * ntj;
   const int grid = (int)std::min<long long>(nblk, kbuild_grid());
-  kmix_dispatch(kp.mix, [&](auto mix) {
-    constexpr bool MIX = decltype(mix)::value;
+  kmixprod_dispatch_full(kp.mix, kp.prod, [&](auto mix, auto prod) {
+    constexpr bool MIX = decltype(mix)::value, PROD = decltype(prod)::value;
     if (same)
-      kmat_symg_kernel<SC, ACC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
+      kmat_symg_kernel<SC, ACC, MIX, PROD><<<grid, 256, lds_bytes, ctx->stream>>>(
           kp, S, g.A, g.B, g.nrmA, g.nbA, n, K, (size_t)ldk, (int)nblk);
     else
-      kmat_crossg_kernel<SC, ACC, MIX><<<grid, 256, lds_bytes, ctx->stream>>>(
+      kmat_crossg_kernel<SC, ACC, MIX, PROD><<<grid, 256, lds_bytes, ctx->stream>>>(
           kp, S, g.A, g.B, g.nrmA, g.nrmB, g.nbA, g.nbB, n, m, K, (size_t)ldk, nti, (int)nblk);
   });
   LAUNCH_CHECK(ctx);
@@ -1338,8 +1416,12 @@ int launch_gram_upper(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, 
   GPR_TRY(gram_prepare(ctx, kp, S, xs, n, nullptr, n, 1, &g));
   const int grid = (int)std::max(1LL, std::min((long long)(kl->nitems + 3) / 4, 256LL * wgs));
   const size_t lds = sizeof(double) * ((256 + 4 * KU_W) * NSE + (colstore ? 4 * 16 * KU_SP : 0));
-  kmat_symu_kernel<S, NSE><<<grid, 256, lds, ctx->stream>>>(
-      kp, g.A, g.B, g.nrmA, g.nbA, n, K, (size_t)ldk, kl->d, kl->nitems, full, colstore);
+  auto* kern = &kmat_symu_kernel<S, NSE>;
+  if constexpr (NSE == 2) {  // the two parts are one product term
+    if (kp.prod) kern = &kmat_symu_kernel<S, NSE, true>;
+  }
+  kern<<<grid, 256, lds, ctx->stream>>>(kp, g.A, g.B, g.nrmA, g.nbA, n, K, (size_t)ldk, kl->d,
+                                        kl->nitems, full, colstore);
   LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1372,10 +1454,11 @@ int launch_gram_any(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, co
 // the kernels any description of <= KMAXP parts takes, without the noise; then one accumulate
 // launch per further group of up to KMAXP parts, the last of which adds sigma_n^2 (add_noise!
 // comes after the part sum, src/compose_covar.jl:52-71).  xs / xps: all parts' scaled points.
+// Groups are cut at term boundaries (kparams_group_count): a product term stays in one launch.
 int launch_gram_groups(gpr_ctx* ctx, const KParams& kp, const double* xs, int n,
                        const double* xps, int m, int same, double* K, int ldk) {
-  for (int p0 = 0; p0 < kp.nse; p0 += KMAXP) {
-    const int cnt = std::min(KMAXP, kp.nse - p0);
+  for (int p0 = 0, cnt = 0; p0 < kp.nse; p0 += cnt) {
+    cnt = kparams_group_count(kp, p0);
     const bool last = p0 + cnt >= kp.nse;
     const KParams g = kparams_group(kp, p0, cnt, last ? kp.has_noise : 0);
     const double* gx = xs + (size_t)p0 * n * kp.d;
@@ -1592,13 +1675,16 @@ int gpr_kernel_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
         return 0;
       }
       GPR_TRY(scale_inputs(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));
-      kgrad_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, ctx->dxs, n, se, local, dDK,
+      int t0 = se, t1 = se;  // the part's term: parts [t0, t1]
+      while (t0 > 0 && !kp_closes(kp, t0 - 1)) --t0;
+      while (!kp_closes(kp, t1)) ++t1;
+      kgrad_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, ctx->dxs, n, se, t0, t1, local, dDK,
                                                     (size_t)ld);
       LAUNCH_CHECK(ctx);
       return 0;
     }
     off += w;
-    if (kinds[t] != GPR_WN) ++se;
+    if (kind_stationary(kinds[t])) ++se;
   }
   return set_err(ctx, GPR_E_ARG, "hp index not found");
 }

@@ -18,15 +18,17 @@ inline bool kind_stationary(int kind) {
 }
 // hyper-parameters of one part: [sigma, l_1..l_d] (SquaredExp, Matern), [sigma, l_1..l_d,
 // p_1..p_d] (Periodic), [sigma_n] (WhiteNoise)
+// (a product marker GPR_MUL owns none)
 inline int kind_hp_width(int kind, int d) {
-  return kind == GPR_WN ? 1 : kind == GPR_PER ? 2 * d + 1 : d + 1;
+  return kind == GPR_MUL ? 0 : kind == GPR_WN ? 1 : kind == GPR_PER ? 2 * d + 1 : d + 1;
 }
 inline int kind_profile(int kind) {
   return kind == GPR_M32 ? KPROF_M32 : kind == GPR_M52 ? KPROF_M52 : KPROF_SE;
 }
 inline const char* kind_name(int kind) {
   return kind == GPR_SE ? "SquaredExp" : kind == GPR_M32 ? "Matern32" : kind == GPR_M52 ? "Matern52"
-         : kind == GPR_PER ? "Periodic" : kind == GPR_WN ? "WhiteNoise" : "?";
+         : kind == GPR_PER ? "Periodic" : kind == GPR_WN ? "WhiteNoise"
+         : kind == GPR_MUL ? "a product marker (GPR_MUL)" : "?";
 }
 
 // Kernel description passed BY VALUE to every assembly kernel (a few dozen bytes of kernargs;
@@ -71,6 +73,12 @@ struct KParams {
   int nper;           // number of Periodic parts
   const double* per;  // [nse]    1.0 for a Periodic part, else 0.0 (null when nper == 0)
   const double* pk;   // [nse][d] periods p_k (1.0 for the other parts; null when nper == 0)
+  // Product terms (appended: descriptions without a GPR_MUL marker pass the fields above
+  // unchanged, with prod = 0 and every part closing a term of its own).  A kernel is a sum of
+  // terms, a term the product of 1..KMAXP consecutive stationary parts (its factors).
+  int prod;           // some term of this description (of the group, where narrowed) has > 1 factor
+  int tendm;          // bit p: part p of sigma[] / prof[] (the launch's group) closes its term
+  const double* tend; // [nse]    1.0 where the part closes its term, else 0.0
 };
 
 // The description as the K-assembly kernels take it: they read kp.d features per scaled point,
@@ -86,7 +94,7 @@ inline KParams kparams_features(const KParams& kp) {
 inline double kp_sigma(const KParams& kp, int p, int* prof = nullptr) {
   int off = 0, se = 0;
   for (int i = 0; i < kp.nk; ++i) {
-    if (kp.kinds[i] != GPR_WN) {
+    if (kind_stationary(kp.kinds[i])) {
       if (se++ == p) {
         if (prof) *prof = kind_profile(kp.kinds[i]);
         return kp.hp[off];
@@ -97,31 +105,60 @@ inline double kp_sigma(const KParams& kp, int p, int* prof = nullptr) {
   if (prof) *prof = KPROF_SE;
   return 0.0;
 }
-// the first part that is not SquaredExp / WhiteNoise (its kind: Matern or Periodic), or 0: the
+// the first entry that is not SquaredExp / WhiteNoise (its kind: Matern, Periodic or a product
+// marker), or 0: the
 // calls that rely on SE's separability or its closed-form integrals refuse such a description
 // (GPR_E_UNSUP)
 inline int kinds_first_non_se(const int* kinds, int nk, int* index) {
   for (int i = 0; i < nk; ++i)
-    if (kinds[i] == GPR_M32 || kinds[i] == GPR_M52 || kinds[i] == GPR_PER) {
+    if (kinds[i] == GPR_M32 || kinds[i] == GPR_M52 || kinds[i] == GPR_PER || kinds[i] == GPR_MUL) {
       if (index) *index = i;
       return kinds[i];
     }
   return 0;
 }
 
-// The description narrowed to stationary parts [p0, p0 + cnt) (cnt <= KMAXP) for one launch of
-// the fused kernels: sigma[], prof[] and the device tables start at part p0 (a profile follows
-// its part); mix is the group's own; has_noise as given.
+// does stationary part p close its term (host side: no GPR_MUL marker follows it)?
+inline bool kp_closes(const KParams& kp, int p) {
+  int se = 0;
+  for (int i = 0; i < kp.nk; ++i)
+    if (kind_stationary(kp.kinds[i]) && se++ == p)
+      return !(i + 1 < kp.nk && kp.kinds[i + 1] == GPR_MUL);
+  return true;
+}
+// The parts of the launch group that starts at part p0 (the first part of a term): whole terms
+// while they fit in KMAXP parts, so that a term never straddles two launches.  Without a marker
+// every term is one part and this is min(KMAXP, nse - p0).
+inline int kparams_group_count(const KParams& kp, int p0) {
+  int cnt = 0;
+  while (p0 + cnt < kp.nse) {
+    int len = 1;
+    while (!kp_closes(kp, p0 + cnt + len - 1)) ++len;
+    if (cnt + len > KMAXP) break;
+    cnt += len;
+  }
+  return cnt;
+}
+
+// The description narrowed to stationary parts [p0, p0 + cnt) (cnt <= KMAXP, whole terms:
+// kparams_group_count) for one launch of the fused kernels: sigma[], prof[], the term mask and
+// the device tables start at part p0 (a profile follows its part); mix and prod are the group's
+// own; has_noise as given.
 inline KParams kparams_group(const KParams& kp, int p0, int cnt, int has_noise) {
   KParams g = kp;
   g.nse = cnt;
   g.has_noise = has_noise;
   g.mix = 0;
+  g.prod = 0;
+  g.tendm = 0;
   for (int p = 0; p < KMAXP; ++p) {
     g.prof[p] = KPROF_SE;
     g.sigma[p] = p < cnt ? kp_sigma(kp, p0 + p, &g.prof[p]) : 0.0;
     if (g.prof[p] != KPROF_SE) g.mix = 1;
+    if (p >= cnt || kp_closes(kp, p0 + p)) g.tendm |= 1 << p;
+    else g.prod = 1;
   }
+  g.tend = kp.tend + p0;
   g.l = kp.l + (size_t)p0 * kp.dx;
   g.l2 = kp.l2 + (size_t)p0 * kp.dx;
   g.sig = kp.sig + p0;
@@ -136,7 +173,8 @@ inline KParams kparams_group(const KParams& kp, int p0, int cnt, int has_noise) 
 // Per-context parameter block: NSLOT device slots of `cap` doubles ([l | l2 | sigma | profile]
 // of one kernel description each; the profile codes are part of the block, so that the
 // comparison with the description made last tells SquaredExp from Matern at equal hp; with a
-// Periodic part [is periodic | p] follow, see make_kparams) and as many pinned host staging slots.  make_kparams fills host
+// Periodic part [is periodic | p] follow, see make_kparams; last the term table [closes its term],
+// which tells SE + PER from SE * PER at equal hp) and as many pinned host staging slots.  make_kparams fills host
 // slot `next`, uploads it in stream order and records ev[next] -- unless the tables equal those
 // of the description made last, whose slot then serves again; a slot is re-filled only once
 // its previous upload has completed (NSLOT descriptions later: the wait does not block in
@@ -152,6 +190,7 @@ struct KParBlock {
   int last = -1;           // slot of the description made last (its host copy is compared), or -1
   size_t last_need = 0;    // its length in doubles
   int last_nper = 0;       // its number of Periodic parts (the two block layouts can be equally long)
+  int last_nse = 0, last_d = 0;  // its stationary parts and input dimension (the same)
   std::vector<double> tmp; // the description being made
 };
 

@@ -91,9 +91,27 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   if (!hp) return set_err(ctx, GPR_E_ARG, "hp is NULL");
   if (d <= 0) return set_err(ctx, GPR_E_ARG, "d=%d (needs d >= 1)", d);
   memset(kp, 0, sizeof *kp);
-  int nse = 0, nper = 0;
+  int nse = 0, nper = 0, nfac = 0;  // nfac: factors of the term being read
   for (int i = 0, off = 0; i < nk; ++i) {
-    if (kind_stationary(kinds[i])) ++nse;
+    if (kinds[i] == GPR_MUL) {  // an infix marker: a stationary part on either side
+      if (i == 0 || i == nk - 1)
+        return set_err(ctx, GPR_E_ARG, "kinds[%d]: a product marker (GPR_MUL) is %s of the "
+                                       "description", i, i == 0 ? "the first entry" : "the last entry");
+      if (kinds[i - 1] == GPR_MUL)
+        return set_err(ctx, GPR_E_ARG, "kinds[%d]: two product markers (GPR_MUL) in a row", i);
+      if (kinds[i - 1] == GPR_WN || kinds[i + 1] == GPR_WN)
+        return set_err(ctx, GPR_E_ARG, "kinds[%d]: a product marker (GPR_MUL) next to WhiteNoise "
+                                       "(kinds[%d]); products take stationary factors only", i,
+                       kinds[i - 1] == GPR_WN ? i - 1 : i + 1);
+      continue;
+    }
+    if (kind_stationary(kinds[i])) {
+      ++nse;
+      nfac = (i > 0 && kinds[i - 1] == GPR_MUL) ? nfac + 1 : 1;
+      if (nfac > KMAXP)
+        return set_err(ctx, GPR_E_UNSUP, "kinds[%d]: factor %d of a product term (at most %d "
+                                         "factors per term)", i, nfac, KMAXP);
+    }
     else if (kinds[i] != GPR_WN) return set_err(ctx, GPR_E_ARG, "unknown kernel kind %d", kinds[i]);
     if (kinds[i] == GPR_PER) {  // (before anything is computed or written)
       ++nper;
@@ -112,14 +130,16 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   // this description's slot of the parameter block:
   // [l (nse d) | l2 (nse d) | sigma (nse) | profile (nse)], then with a Periodic part
   // [is periodic (nse) | p (nse d)] -- a longer block, so that it never compares equal to one
-  // without, and two Periodic parts that differ only in p differ in the block
+  // without, and two Periodic parts that differ only in p differ in the block; last the term
+  // table [closes its term (nse)]: 1.0 unless a product marker follows the part
   KParBlock& kb = ctx->kpar;
   const size_t nl = (size_t)nse * d;
-  const size_t need = 2 * nl + 2 * (size_t)nse + (nper ? nl + (size_t)nse : 0);
+  const size_t ntab = 2 * nl + 2 * (size_t)nse + (nper ? nl + (size_t)nse : 0);  // before tend
+  const size_t need = ntab + (size_t)nse;
   if (need > kb.cap || !kb.dev) {
     // (first use, or a description past every earlier one: never inside the 4 x 64 envelope
     // once the block exists)
-    const size_t cap = std::max(need, (size_t)(2 * 4 * 64 + 2 * 4));
+    const size_t cap = std::max(need, (size_t)(2 * 4 * 64 + 3 * 4));
     if (kb.dev) {
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       HIP_TRY(ctx, hipFree(kb.dev));
@@ -151,12 +171,18 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   kp->nk = nk;
   kp->hp = hp;
   int off = 0;
+  kp->tendm = (1 << KMAXP) - 1;
   for (int i = 0; i < nk; ++i) {
+    if (kinds[i] == GPR_MUL) continue;
     if (kinds[i] != GPR_WN) {
       const int prof = kind_profile(kinds[i]);
+      const bool closes = !(i + 1 < nk && kinds[i + 1] == GPR_MUL);
+      if (!closes) kp->prod = 1;
+      hl[ntab + kp->nse] = closes ? 1.0 : 0.0;
       if (kp->nse < KMAXP) {
         kp->sigma[kp->nse] = hp[off];
         kp->prof[kp->nse] = prof;
+        if (!closes) kp->tendm &= ~(1 << kp->nse);
       }
       if (prof != KPROF_SE) kp->mix = 1;
       hl[2 * nl + kp->nse] = hp[off];
@@ -185,7 +211,8 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
   // the tables of the description made last on this context (a fit and the gradient or the
   // posterior that follows it share hp): its slot serves again, nothing is uploaded
   int slot = kb.last;
-  if (slot < 0 || kb.last_need != need || kb.last_nper != nper ||
+  if (slot < 0 || kb.last_need != need || kb.last_nper != nper || kb.last_nse != nse ||
+      kb.last_d != d ||
       memcmp(kb.host + (size_t)slot * kb.cap, hl, need * sizeof(double)) != 0) {
     slot = kb.next;
     kb.next = (slot + 1) % KParBlock::NSLOT;
@@ -199,6 +226,8 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
     kb.last = slot;
     kb.last_need = need;
     kb.last_nper = nper;
+    kb.last_nse = nse;
+    kb.last_d = d;
   }
   const double* dl = kb.dev + (size_t)slot * kb.cap;
   kp->l = dl;
@@ -209,6 +238,7 @@ int make_kparams(gpr_ctx* ctx, const int* kinds, int nk, const double* hp, int d
     kp->per = dl + 2 * nl + 2 * nse;
     kp->pk = dl + 2 * nl + 3 * (size_t)nse;
   }
+  kp->tend = dl + ntab;
   if (D_total) *D_total = off;
   return 0;
 }

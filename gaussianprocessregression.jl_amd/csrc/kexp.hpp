@@ -108,6 +108,42 @@ static __device__ __forceinline__ double kprof_s2_w(double D, const double* ts, 
   }
 }
 
+// the same with the profile as a run-time, wave-uniform code (the product-term phases of the
+// gradient kernels, which walk the factors of a term in one loop)
+static __device__ __forceinline__ double kprof_s2_w_rt(int prof, double D, const double* ts,
+                                                       double* W) {
+  if (prof == 1) return kprof_s2_w<1>(D, ts, W);
+  if (prof == 2) return kprof_s2_w<2>(D, ts, W);
+  return kprof_s2_w<0>(D, ts, W);
+}
+
+// The scaled squared distance of one pair for one part, as the gradient kernels' wide passes form
+// it: sum_k l_k^2 r_k^2 on raw x (xa, xb), or for a Periodic part (per, wave-uniform) sum_k l_k^2
+// ((cos a - cos b)^2 + (sin a - sin b)^2) on the unit features (ca, cb: [cos | sin], d each).  Two
+// partial sums, even and odd k.  Used where a product term needs every factor's value per pair.
+static __device__ __forceinline__ double kpair_dist(bool per, int d, const double* __restrict__ l2,
+                                                    const double* __restrict__ xa,
+                                                    const double* __restrict__ xb,
+                                                    const double* __restrict__ ca,
+                                                    const double* __restrict__ cb) {
+  double a0 = 0.0, a1 = 0.0;
+  if (per) {
+    for (int k = 0; k < d; ++k) {
+      const double dc = ca[k] - cb[k], ds = ca[d + k] - cb[d + k];
+      const double t = fma(dc, dc, ds * ds);
+      if (k & 1) a1 = fma(l2[k], t, a1);
+      else a0 = fma(l2[k], t, a0);
+    }
+  } else {
+    for (int k = 0; k < d; ++k) {
+      const double r = xa[k] - xb[k];
+      if (k & 1) a1 = fma(l2[k], r * r, a1);
+      else a0 = fma(l2[k], r * r, a0);
+    }
+  }
+  return a0 + a1;
+}
+
 // the profiles with the library exponential (the difference-form fallback kernels, dK/dtheta):
 // prof is a run-time, wave-uniform code
 static __device__ __forceinline__ double kprof_exact_w(int prof, double s2, double D, double* W) {
@@ -151,6 +187,24 @@ static __device__ __forceinline__ void kprof_dispatch(int prof, F&& f) {
 template <class F>
 static inline auto kmix_dispatch(bool mix, F&& f) {
   return mix ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// Host side of MIX and PROD: f(bool_constant<MIX>, bool_constant<PROD>).  A description with a
+// product term (KParams::prod) launches the MIX instantiation whatever its profiles are -- MIX
+// reads each part's profile at run time, SquaredExp included -- so PROD adds one instantiation
+// per kernel, not two; without a product this is kmix_dispatch.
+template <class F>
+static inline auto kmixprod_dispatch(bool mix, bool prod, F&& f) {
+  if (prod) return f(std::true_type{}, std::true_type{});
+  return mix ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+}
+
+// all four combinations (the Gram tile kernels: a product of SquaredExp-profile parts keeps the
+// MIX = false kernels' launch bounds)
+template <class F>
+static inline auto kmixprod_dispatch_full(bool mix, bool prod, F&& f) {
+  if (prod) return mix ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
+  return mix ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
 }
 
 // the same without the clamp (3 VALU fewer), for callers that have bounded dist < 5.8e6, so

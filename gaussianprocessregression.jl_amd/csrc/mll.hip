@@ -274,9 +274,16 @@ __global__ __launch_bounds__(256) void mll_grad_tiles_kernel(KParams kp, const d
 //     the unrolled wave-uniform column loads cost 50 more SGPR spills for no fewer passes that
 //     matter):
 //     S_lk += mk chord_k^2, S_pk += mk r_k sin(a_k - b_k), sin(a - b) = sin a cos b - cos a sin b.
+// PROD: the description has a product term (launched with MIX: profiles at run time).  Part p is
+// a factor of the term of parts [t0, t1], whose exp tables are filled when the term opens.  Phase
+// 1 evaluates EVERY factor of the term for each of the thread's 16 pairs (kpair_dist), forms the
+// cofactor C = prod_{g != p} K_g as a product, sums mv (K_p C + eps on the diagonal) into S_sigma
+// and leaves mv W_p C as phase 2's weight: a term of F factors costs F^2 evaluations per pair
+// (the cofactor is re-evaluated per factor rather than F value arrays of 16 x 256 held in LDS:
+// DESIGN 3.13).  Phase 2, the slots and the reduction are unchanged.
 constexpr int GW = 32;
 constexpr int GP = 8;
-template <bool MIX, bool PER>
+template <bool MIX, bool PER, bool PROD = false>
 __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const double* __restrict__ X,
                                                             const double* __restrict__ cs, int n,
                                                             const double* __restrict__ Kinv,
@@ -294,13 +301,25 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
   const double* xrow = X + irc * d;
 
   double* out = partial + (size_t)blockIdx.x * nslot;
+  int t0 = 0, t1 = -1;  // PROD: the open term's parts
   for (int p = 0; p < kp.nse; ++p) {
-    if ((p & (KMAXP - 1)) == 0) {  // this group of parts' exp tables
+    if constexpr (PROD) {
+      if (p > t1) {  // part p opens a term: its last factor (<= KMAXP per term), its exp tables
+        t0 = t1 = p;
+        while (t1 + 1 < kp.nse && t1 - t0 + 1 < KMAXP &&
+               __builtin_amdgcn_readfirstlane((int)kp.tend[t1]) == 0)
+          ++t1;
+        __syncthreads();
+        for (int g = t0; g <= t1; ++g)
+          tabs[g - t0][threadIdx.x] = (kp.sig[g] * kp.sig[g]) * kp.exptab[threadIdx.x];
+        __syncthreads();
+      }
+    } else if ((p & (KMAXP - 1)) == 0) {  // this group of parts' exp tables
       __syncthreads();
       grad_fill_tabs(kp, p, tabs);
       __syncthreads();
     }
-    const double* ts = tabs[p & (KMAXP - 1)];
+    const double* ts = tabs[PROD ? p - t0 : p & (KMAXP - 1)];
     const double* l2p = kp.l2 + (size_t)p * d;
     const bool per = PER && __builtin_amdgcn_readfirstlane((int)kp.per[p]) != 0;
     // this part's unit features (cs is null without a Periodic part)
@@ -309,7 +328,7 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
     // phase 1: the 16 weights.  A Periodic part's 16 distances first, GP dimensions of the row
     // point's cos / sin in registers at a time (the row point is read once per chunk, not once
     // per column), accumulated in the thread's own mks slots
-    if (per) {
+    if (!PROD && per) {
       for (int k0 = 0; k0 < d; k0 += GP) {
         const int kn = min(GP, d - k0);  // wave-uniform
         double cr[GP], sr[GP];
@@ -337,6 +356,34 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
       }
     }
     double acc_s = 0.0;
+    if constexpr (PROD) {
+#pragma unroll 1
+      for (int c = 0; c < 16; ++c) {
+        const int jr = j0 + wv + 4 * c;
+        const int j = min(jr, n - 1);  // wave-uniform
+        const double kin = Kinv[irc + (size_t)j * ldk];
+        const double mv = (irow && jr < n) ? wgt * (ai * alpha[j] - kin) : 0.0;
+        double Kp = 0.0, Wp = 0.0, C = 1.0;
+        for (int g = t0; g <= t1; ++g) {
+          const bool perg = PER && __builtin_amdgcn_readfirstlane((int)kp.per[g]) != 0;
+          const double* csg = PER ? cs + (size_t)g * n * de : nullptr;
+          const double dist = kpair_dist(perg, d, kp.l2 + (size_t)g * d, xrow, X + (size_t)j * d,
+                                         PER ? csg + irc * de : nullptr,
+                                         PER ? csg + (size_t)j * de : nullptr);
+          double Wg;
+          const double Kg = kprof_s2_w_rt(__builtin_amdgcn_readfirstlane((int)kp.pf[g]), dist,
+                                          tabs[g - t0], &Wg);
+          if (g == p) {
+            Kp = Kg;
+            Wp = Wg;
+          } else {
+            C *= Kg;
+          }
+        }
+        acc_s += mv * (Kp * C + (i == j ? kp.eps : 0.0));
+        mks[c][threadIdx.x] = mv * (Wp * C);  // phase 2's weight
+      }
+    } else {
     kprof_dispatch<MIX>(MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0, [&](auto pf) {
 #pragma unroll 1
     for (int c = 0; c < 16; ++c) {
@@ -373,6 +420,7 @@ __global__ __launch_bounds__(256) void mll_grad_wide_kernel(KParams kp, const do
       acc_s += mk;
     }
     });
+    }
     for (int o = 32; o > 0; o >>= 1) acc_s += __shfl_xor(acc_s, o);
     if (per) {
       // phase 2, Periodic: both sums (acc[k], acc[GP + k]) of GP dimensions at a time
@@ -469,7 +517,13 @@ void launch_grad_pass(gpr_ctx* ctx, const KParams& kp, const double* X, const do
     auto* k = d == D ? &mll_grad_tiles_kernel<D, true, MIX> : &mll_grad_tiles_kernel<D, false, MIX>;
     k<<<grid, 256, 0, ctx->stream>>>(kp, X, n, Kinv, (size_t)ldk, alpha, partial, nslot);
   };
-  if (kp.nper)
+  if (kp.prod) {  // (a product term: the wide kernel's PROD form, profiles at run time)
+    if constexpr (MIX) {
+      auto* k = kp.nper ? &mll_grad_wide_kernel<true, true, true> : &mll_grad_wide_kernel<true, false, true>;
+      k<<<grid, 256, 0, ctx->stream>>>(kp, X, kp.nper ? cs : nullptr, n, Kinv, (size_t)ldk, alpha,
+                                       partial, nslot);
+    }
+  } else if (kp.nper)
     mll_grad_wide_kernel<MIX, true><<<grid, 256, 0, ctx->stream>>>(kp, X, cs, n, Kinv, (size_t)ldk,
                                                                     alpha, partial, nslot);
   else if (d <= 2) tiles(std::integral_constant<int, 2>{});
@@ -516,7 +570,7 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   {
     TimerScope ts(ctx, TC_OTHER, 0.0);
     if (kp.nper) GPR_TRY(launch_embed_unit(ctx, kp, dX, n));  // (into ctx->dxs)
-    kmix_dispatch(kp.mix, [&](auto mix) {
+    kmix_dispatch(kp.mix || kp.prod, [&](auto mix) {
       launch_grad_pass<decltype(mix)::value>(ctx, kp, dX, ctx->dxs, n, dKinv, ldk, dalpha, partial,
                                              nslot, nblk);
     });
@@ -530,6 +584,7 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   // assemble in hp order (kinds order)
   int off = 0, so = 0;
   for (int t = 0; t < nk; ++t) {
+    if (kinds[t] == GPR_MUL) continue;  // (a marker owns neither hp nor slots)
     if (kinds[t] != GPR_WN) {
       const double* ss = s.data() + so;
       const double sig = hp[off];

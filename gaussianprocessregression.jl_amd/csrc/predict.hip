@@ -127,13 +127,17 @@ int launch_fill(gpr_ctx* ctx, double* p, size_t n, double v) {
 }
 
 // diagonal-variance prior: sigma^2 for a single stationary part (src/predict.jl:67); composed kernels:
-// sum over ALL parts of hp_part[1]^2, noise included (src/predict.jl:56-58).  No eps.
+// sum over ALL parts of hp_part[1]^2, noise included (src/predict.jl:56-58).  No eps.  A product
+// term (factors joined by GPR_MUL markers) contributes the product of its factors' sigma^2.
 double diag_prior(const int* kinds, int nk, const double* hp, int d) {
   if (nk == 1) return hp[0] * hp[0];
-  double s = 0.0;
+  double s = 0.0, term = 0.0;
   int off = 0;
   for (int t = 0; t < nk; ++t) {
-    s += hp[off] * hp[off];
+    if (kinds[t] == GPR_MUL) continue;
+    const double s2 = hp[off] * hp[off];
+    term = (t > 0 && kinds[t - 1] == GPR_MUL) ? term * s2 : s2;
+    if (!(t + 1 < nk && kinds[t + 1] == GPR_MUL)) s += term;
     off += kind_hp_width(kinds[t], d);
   }
   return s;

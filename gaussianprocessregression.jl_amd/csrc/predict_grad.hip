@@ -20,6 +20,7 @@
 // own partial sums partial[(slab index, wave)][j][k] -- no atomics -- and pgrad_reduce_kernel adds
 // the slots in a fixed order: two calls on the same inputs agree bit for bit.
 #include <cmath>
+#include <vector>
 
 #include "common.hpp"
 #include "kexp.hpp"
@@ -148,7 +149,11 @@ __global__ __launch_bounds__(256) void pgrad_tiles_kernel(KParams kp, const doub
 //     own partial slot in global memory (read and written by this thread alone, in program order).
 // cs / csp: per part and training / test point the unit features [cos a_k | sin a_k], a_k =
 // 2 pi x_k / p_k (embed_inputs_kernel's unit form; only Periodic parts' rows are read).
-template <bool MIX, bool PER, bool QW>
+// PROD: the launch's group holds a product term (launched with MIX: profiles at run time; a
+// term never straddles two groups).  Phase 1 evaluates every factor of part p's term [t0, t1]
+// for the pair (kpair_dist), forms the cofactor C = prod_{g != p} K_g as a product and leaves
+// w W_p C for phase 2, which is unchanged for both branches.
+template <bool MIX, bool PER, bool QW, bool PROD = false>
 __global__ __launch_bounds__(256) void pgrad_wide_kernel(KParams kp, const double* __restrict__ X,
                                                          const double* __restrict__ cs, int n,
                                                          const double* __restrict__ Xp,
@@ -189,6 +194,32 @@ __global__ __launch_bounds__(256) void pgrad_wide_kernel(KParams kp, const doubl
       const double* ctr = PER ? cs + (size_t)p * n * de : nullptr;
       const double* crow = PER ? csp + ((size_t)p * m + jc) * de : nullptr;
       // phase 1
+      if constexpr (PROD) {
+        int t0 = p, t1 = p;  // the part's term (kp.tendm: the group's mask, wave-uniform)
+        while (t0 > 0 && !((kp.tendm >> (t0 - 1)) & 1)) --t0;
+        while (t1 + 1 < kp.nse && !((kp.tendm >> t1) & 1)) ++t1;
+#pragma unroll 1
+        for (int c = 0; c < 16; ++c) {
+          const int ir = i0 + wv + 4 * c;
+          const int i = min(ir, n - 1);  // wave-uniform
+          double w;
+          if (QW) w = qs[lane][wv + 4 * c];
+          else w = wsrc[i];
+          if (ir >= i_end) w = 0.0;
+          double Wp = 0.0, C = 1.0;
+          for (int g = t0; g <= t1; ++g) {
+            const bool perg = PER && __builtin_amdgcn_readfirstlane((int)kp.per[g]) != 0;
+            const double dist = kpair_dist(perg, d, kp.l2 + (size_t)g * d, xrow, X + (size_t)i * d,
+                                           PER ? csp + ((size_t)g * m + jc) * de : nullptr,
+                                           PER ? cs + ((size_t)g * n + i) * de : nullptr);
+            double Wg;
+            const double Kg = kprof_s2_w_rt(kp.prof[g], dist, tabs[g], &Wg);
+            if (g == p) Wp = Wg;
+            else C *= Kg;
+          }
+          mks[c][threadIdx.x] = w * (Wp * C);
+        }
+      } else
       kprof_dispatch<MIX>(MIX ? __builtin_amdgcn_readfirstlane((int)kp.pf[p]) : 0, [&](auto pf) {
 #pragma unroll 1
         for (int c = 0; c < 16; ++c) {
@@ -312,7 +343,13 @@ void launch_pgrad_group(gpr_ctx* ctx, const KParams& kp, const double* X, const 
     auto* k = d == D ? &pgrad_tiles_kernel<D, true, MIX, QW> : &pgrad_tiles_kernel<D, false, MIX, QW>;
     k<<<grid, 256, 0, ctx->stream>>>(kp, X, n, Xp, m, wsrc, (size_t)n, slab, partial);
   };
-  if (kp.nper)
+  if (kp.prod) {  // (a product term in the group: the wide kernel's PROD form)
+    if constexpr (MIX) {
+      auto* k = kp.nper ? &pgrad_wide_kernel<true, true, QW, true> : &pgrad_wide_kernel<true, false, QW, true>;
+      k<<<grid, 256, 0, ctx->stream>>>(kp, X, kp.nper ? cs : nullptr, n, Xp, kp.nper ? csp : nullptr,
+                                       m, wsrc, (size_t)n, slab, partial);
+    }
+  } else if (kp.nper)
     pgrad_wide_kernel<MIX, true, QW><<<grid, 256, 0, ctx->stream>>>(kp, X, cs, n, Xp, csp, m, wsrc,
                                                                    (size_t)n, slab, partial);
   else if (d <= 2) tiles(std::integral_constant<int, 2>{});
@@ -334,18 +371,21 @@ int pgrad_pass(gpr_ctx* ctx, const KParams& kp, const double* X, const double* c
   const int d = kp.dx;
   const int slab = (std::max(ctx->pgrad_slab, PT) + PT - 1) / PT * PT;
   const int nslab = (n + slab - 1) / slab;
-  const int ngroup = (kp.nse + KMAXP - 1) / KMAXP;
+  // (groups of up to KMAXP parts, cut at term boundaries: a product term stays in one launch)
+  std::vector<int> gp0;
+  for (int p0 = 0; p0 < kp.nse; p0 += kparams_group_count(kp, p0)) gp0.push_back(p0);
+  const int ngroup = (int)gp0.size();
   const size_t len = (size_t)m * d;
   const size_t per_group = (size_t)nslab * 4 * len;
   GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, per_group * ngroup + 64));
   double* partial = ctx->dscratch;
   TimerScope ts(ctx, timing_class, 0.0);
   for (int g = 0; g < ngroup; ++g) {
-    const int p0 = g * KMAXP;
-    const KParams kg = kparams_group(kp, p0, std::min(KMAXP, kp.nse - p0), 0);
+    const int p0 = gp0[g];
+    const KParams kg = kparams_group(kp, p0, kparams_group_count(kp, p0), 0);
     const double* csg = cs ? cs + (size_t)p0 * n * kp.de : nullptr;
     const double* cspg = csp ? csp + (size_t)p0 * m * kp.de : nullptr;
-    kmix_dispatch(kg.mix, [&](auto mix) {
+    kmix_dispatch(kg.mix || kg.prod, [&](auto mix) {
       constexpr bool MIX = decltype(mix)::value;
       if (qw)
         launch_pgrad_group<MIX, true>(ctx, kg, X, csg, n, Xp, cspg, m, wsrc, slab, nslab,

@@ -19,6 +19,7 @@ from .core import (
     Matern32,
     Matern52,
     Periodic,
+    ProductKernel,
     is_stationary,
     part_dim_hp,
     MllGradCache,

@@ -23,6 +23,7 @@ GPR_WN = 2
 GPR_M32 = 3  # Matern-3/2
 GPR_M52 = 4  # Matern-5/2
 GPR_PER = 5  # Periodic
+GPR_MUL = 6  # product marker between two stationary factors of one term
 GPR_CROSS = 0        # gpr_kernel `same`: kernel!(K, cov, hp, x, xp), x !== xp
 GPR_SELF = 1         # kernel!(K, cov, hp, x): eps per SE part + noise
 GPR_SAME_OBJECT = 2  # kernel!(K, cov, hp, x, x), x === xp: eps per SE part, no noise

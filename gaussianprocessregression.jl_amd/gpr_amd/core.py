@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GPR_M32, GPR_M52, GPR_PER, GPR_SE, GPR_WN, GprError, PosDefException, lib
+from ._lib import GPR_M32, GPR_M52, GPR_MUL, GPR_PER, GPR_SE, GPR_WN, GprError, PosDefException, lib
 
 F64 = torch.float64
 EPS_DEFAULT = 1e-8
@@ -117,11 +117,34 @@ class AbstractKernel:
     def __add__(self, other):
         return ComposedKernel(self.parts() + other.parts())
 
+    def __mul__(self, other):
+        """A product term: `SquaredExp() * Periodic()`.  Products of products flatten; sums are
+        not distributed."""
+        for k in (self, other):
+            if isinstance(k, ComposedKernel):
+                raise TypeError(
+                    f"cannot multiply a sum of kernels ({k!r}): `*` is not distributed over `+`, "
+                    "because that would duplicate hyper-parameters; write the sum of products out")
+            if not isinstance(k, AbstractKernel):
+                return NotImplemented
+        return ProductKernel(self.factors() + other.factors())
+
     def parts(self):
+        """The summands, in `+` order (a product term is one summand)."""
+        return (self,)
+
+    def factors(self):
+        """The factors of this summand, in `*` order (a plain kernel: itself)."""
         return (self,)
 
     def kinds(self):
-        return [p.KIND for p in self.parts()]
+        """The C ABI's description: the parts' codes in `+` order, the factors of a product
+        term joined by GPR_MUL markers."""
+        out = []
+        for p in self.parts():
+            for j, f in enumerate(p.factors()):
+                out += ([GPR_MUL] if j else []) + [f.KIND]
+        return out
 
 
 class SquaredExp(AbstractKernel):
@@ -214,6 +237,37 @@ class ComposedKernel(AbstractKernel):
         return " + ".join(repr(k) for k in self.kernels)
 
 
+class ProductKernel(AbstractKernel):
+    """Product of 2..4 stationary kernels in `*` order, one summand of a kernel: K = prod_f
+    sigma_f^2 f_f(D_f), eps once per term on a same-object diagonal.  hp is the concatenation of
+    the factors' own layouts, so a product of F factors has F sigmas of which only the product
+    is identifiable (accepted: nothing is tied)."""
+    KIND = GPR_MUL  # (never WhiteNoise; `kinds()` writes the marker between the factors)
+
+    def __init__(self, factors: Sequence[AbstractKernel]):
+        factors = tuple(factors)
+        for f in factors:
+            if isinstance(f, (ComposedKernel, ProductKernel)) or not isinstance(f, AbstractKernel):
+                raise TypeError(f"a product's factors are plain stationary kernels, not {f!r}")
+            if f.KIND == GPR_WN:
+                raise TypeError("WhiteNoise cannot be a factor of a product: add it as a summand")
+        if len(factors) < 2:
+            raise TypeError("a product needs at least two factors")
+        self._factors = factors
+
+    def factors(self):
+        return self._factors
+
+    def __eq__(self, o):
+        return isinstance(o, ProductKernel) and o._factors == self._factors
+
+    def __hash__(self):
+        return hash(("MUL",) + self._factors)
+
+    def __repr__(self):
+        return " * ".join(repr(f) for f in self._factors)
+
+
 def is_stationary(k: AbstractKernel) -> bool:
     """SquaredExp, Matern32, Matern52: a radial profile of the ARD-scaled distance, hp =
     [sigma, l_1..l_d]; Periodic: hp = [sigma, l_1..l_d, p_1..p_d].  Every rule the reference
@@ -223,7 +277,10 @@ def is_stationary(k: AbstractKernel) -> bool:
 
 def part_dim_hp(k: AbstractKernel, dim: int) -> int:
     """Hyperparameters of one part: WhiteNoise 1, Periodic 2 dim + 1, the other stationary
-    parts dim + 1.  Every split of a flat hp vector goes through this."""
+    parts dim + 1, a product term the sum over its factors.  Every split of a flat hp vector
+    goes through this."""
+    if isinstance(k, ProductKernel):  # the factors' own layouts, concatenated
+        return sum(part_dim_hp(f, dim) for f in k.factors())
     if k.KIND == GPR_WN:
         return 1
     return 2 * dim + 1 if k.KIND == GPR_PER else dim + 1

@@ -16,7 +16,8 @@
  *     and the flat hyper-parameter vector `hp` (HOST pointer) of length sum(dim_hp) -- SE, M32,
  *     M52: d+1 ([sigma, l_1..l_d]), PER: 2d+1 ([sigma, l_1..l_d, p_1..p_d]), WN: 1 ([sigma_n])
  *     -- exactly split(hp, dims)
- *     (src/compose_covar.jl:21-28).
+ *     (src/compose_covar.jl:21-28).  A GPR_MUL entry between two stationary parts multiplies them
+ *     (product terms, below); it counts in nk and owns no hyper-parameters.
  *   - Pointers named d* are DEVICE pointers (from gpr_malloc, hipMalloc, or a torch
  *     tensor); all other pointers are host pointers.  No pointer is retained after a call
  *     returns.
@@ -43,6 +44,7 @@ extern "C" {
 #define GPR_M32 3 /* Matern-3/2 (no counterpart in the reference: defined below) */
 #define GPR_M52 4 /* Matern-5/2 */
 #define GPR_PER 5 /* Periodic (no counterpart in the reference: defined below) */
+#define GPR_MUL 6 /* product marker between two stationary factors (defined below) */
 
 #define GPR_OK 0
 #define GPR_E_ARG (-1)      /* bad argument (message names it)                      */
@@ -94,8 +96,29 @@ extern "C" {
  * with W as above (GPR_PER: W = k).  A Matern part at a coincident point has a finite W and
  * r = 0, so the term is 0.  A WhiteNoise part contributes nothing: the cross kernel has no noise.
  *
+ * Product terms (GPR_MUL, no counterpart in the reference).  A kernel is a sum of TERMS; a term is
+ * one GPR_WN or the product of 1 to 4 stationary factors.  GPR_MUL is an infix marker inside
+ * kinds[]: {GPR_SE, GPR_MUL, GPR_PER, GPR_WN} is SE * PER + WN.  A description without a marker
+ * means exactly what it meant before (every part a term of its own).  hp stays the concatenation
+ * of the parts' own layouts in order, markers skipped: each factor keeps its [sigma, l_1..l_d]
+ * (GPR_PER: [sigma, l.., p..]), so a product of F factors has F sigmas of which only the product
+ * is identifiable -- accepted; nothing is tied and there is no "constant" kind.
+ * With k_f = sigma_f^2 f_f(D_f) the factor's value without eps:
+ *   T = prod_f k_f, plus eps ONCE PER TERM on a same-object diagonal (the rule "eps once per
+ *   stationary part" with "part" read as "summand"; a term of one factor is unchanged bit for bit);
+ *   K = the terms added in order; the noise is the first GPR_WN's sigma_n^2 in the GPR_SELF form;
+ *   the diagonal-variance prior is the sum over terms of prod_f sigma_f^2 (GPR_WN: sigma_n^2).
+ * Derivatives, for factor f of term T with the cofactor C_f = prod_{g != f} k_g (formed as a
+ * product, never as T / k_f, which underflows):
+ *   dK/dsigma_f = (2 / |sigma_f|) T           (T with its eps on a same-object diagonal)
+ *   dK/dl_k, dK/dp_k, dk/dx*_k: factor f's own formula above with W_f C_f for W_f; dk/dx*_k of a
+ *   term is the sum of these over its factors.  LogScale is unchanged (G .*= hp).
+ * Refused before anything is computed or written -- GPR_E_ARG, the message names the position in
+ * kinds[]: a marker first, last or doubled, a marker next to GPR_WN; GPR_E_UNSUP: a term of more
+ * than 4 factors.  `*` is not distributed over `+` (that would duplicate hyper-parameters).
+ *
  * Calls built on SquaredExp's separability or its closed-form erf integrals refuse a description
- * with a Matern or Periodic part -- GPR_E_UNSUP, the message names the part, nothing is computed or written:
+ * with a Matern or Periodic part or a product marker -- GPR_E_UNSUP, the message names the part, nothing is computed or written:
  * gpr_split_predict, gpr_split_predict_rows, gpr_split_predict_shard, gpr_split_predict_mgpu,
  * gpr_split_factors, gpr_integrate, gpr_integrate_noise.  (gpr_antideriv_se takes no kinds: it
  * is SquaredExp's integral of whatever hp it is given.) */
