@@ -199,7 +199,7 @@ struct KParBlock {
 enum TimingClass {
   TC_KBUILD = 0, TC_SYRK = 1, TC_PANEL = 2, TC_TRSM_GEMM = 3, TC_OTHER = 4, TC_GEMM_PIPE = 5,
   TC_DAG = 6, TC_DAG_SOLVE = 7, TC_PGRAD_MEAN = 8, TC_PGRAD_VAR = 9, TC_PGRAD_SOLVE = 10,
-  TC_APPEND_SOLVE = 11, TC_N = 12
+  TC_APPEND_SOLVE = 11, TC_REMOVE_UPDATE = 12, TC_N = 13
 };
 
 struct TimedLaunch {
@@ -316,6 +316,8 @@ struct gpr_ctx {
   size_t trsv_cap = 0;
   double* dahand = nullptr;     // the append's skinny solve: hand-off blocks (128 x 16 per block)
   size_t ahand_cap = 0;
+  double* drmw = nullptr;       // gpr_fit_remove: a group's W rows (8 x n'), then keep[] and idx[]
+  size_t rmw_cap = 0;
   double* dxs = nullptr;        // per-part scaled training inputs  (nse x d x n)
   size_t xs_cap = 0;
   double* dxps = nullptr;       // per-part scaled second inputs    (nse x d x m)
@@ -379,6 +381,9 @@ struct gpr_ctx {
   int append_sweep = -1;        // GPR_APPEND_SWEEP: V = U^{-T} K(x, x_new) of gpr_fit_append by the
                                 // single-launch skinny sweep (1, m <= 128), by trsm_ut_core (0),
                                 // -1 auto (append.hip)
+  int remove_sweep = -1;        // GPR_REMOVE_SWEEP: the rank-r update of gpr_fit_remove as one persistent
+                                // launch per group of 8 removed points (1), as one diagonal and one
+                                // panel launch per 128-row block (0), -1 auto = 0 (remove.hip)
 
   bool timing = false;
   std::vector<TimedLaunch> pending;

@@ -281,6 +281,7 @@ const Knob kKnobs[] = {
     {"GPR_PGRAD_SLAB", &gpr_ctx::pgrad_slab, nullptr},
     {"GPR_PGRAD_SOLVE", &gpr_ctx::pgrad_solve, nullptr},
     {"GPR_APPEND_SWEEP", &gpr_ctx::append_sweep, nullptr},
+    {"GPR_REMOVE_SWEEP", &gpr_ctx::remove_sweep, nullptr},
 };
 
 void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
@@ -404,6 +405,7 @@ int gpr_ctx_destroy(gpr_ctx_t ctx) {
   if (ctx->dbig2) hipFree(ctx->dbig2);
   if (ctx->dtrsv) hipFree(ctx->dtrsv);
   if (ctx->dahand) hipFree(ctx->dahand);
+  if (ctx->drmw) hipFree(ctx->drmw);
   if (ctx->dsqinv) hipFree(ctx->dsqinv);
   if (ctx->dpanel) hipFree(ctx->dpanel);
   if (ctx->dxs) hipFree(ctx->dxs);

@@ -39,6 +39,7 @@ from .core import (
     loss,
     loss_grad_,
     append_,
+    remove_,
     predict,
     predict_,
     predict_grad,

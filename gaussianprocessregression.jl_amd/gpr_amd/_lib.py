@@ -76,6 +76,7 @@ _SIGS = {
     "gpr_mll_grad": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _d, _i, _dp]),
     "gpr_fit": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _d, _p, _i, _p, _ip]),
     "gpr_fit_append": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _i, _p, _i, _i, _d, _p, _i, _p, _p, _ip]),
+    "gpr_fit_remove": (_i, [_p, _p, _i, _i, _ip, _i, _p, _i, _i, _p, _i, _p]),
     "gpr_predict": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _d, _p, _p,
                          _i, _p]),
     "gpr_predict_grad": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _d, _p, _p,

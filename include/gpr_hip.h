@@ -160,7 +160,8 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *        variance pass of gpr_predict_grad (its kernels and their fixed-order sum), 10 the solve
  *        that makes its Q (call-level: the launches inside it also count in their own classes),
  *        11 the append's skinny solve (V = U^{-T} K(x, x_new) of gpr_fit_append, whichever route
- *        takes it; call-level too; the flops slot carries n0^2 m).
+ *        takes it; call-level too; the flops slot carries n0^2 m), 12 the rank-r update of
+ *        gpr_fit_remove (its W rows and every launch of either route; call-level).
  *        Returns accumulated ms, launch count, flops (bytes for class 0). */
 /* Knobs: the library's run-time switches.  Each is a GPR_* environment variable read ONCE,
  * when a context is created, and can be changed on a live context with gpr_set_knob (values
@@ -220,6 +221,12 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         columns) or by the GEMM-based solve of gpr_trsm_upper_trans (0); -1 auto:
  *                         the sweep for m <= 48.  Measured at n0 = 32768 - m, sweep vs the GEMM
  *                         route: m = 1 1.78 vs 10.4 ms, 16 2.36 vs 9.0, 48 7.05 vs 9.1, 64 9.39 vs 9.18
+ *   GPR_REMOVE_SWEEP  -1  gpr_fit_remove: the rank-r update of the factor as one persistent launch per
+ *                         group of 8 removed points (1: a workgroup per 128-column block, the
+ *                         rotations handed from block to block inside the launch) or as one diagonal
+ *                         and one panel launch per 128-row block (0); -1 auto: the launch chain,
+ *                         which measured faster at n0 = 32768 (r = 1 oldest: 16.1 vs 19.1 ms per update,
+ *                         r = 128: 316 vs 427).  The two agree bit for bit
  * A gpr_mgpu handle has knobs of its own, read from the environment once at gpr_mgpu_create
  * and changed with gpr_mgpu_set_knob / gpr_mgpu_get_knob (below):
  *   GPR_MGPU_STREAM   -1  1: stream U out during device 0's fit; 0: after it (-1 auto: only
@@ -347,6 +354,32 @@ int gpr_fit_append(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, in
                    const double* dX, int n0, int m, const double* dy, int nrhs, int ldy,
                    double eps, double* dK, int ldk, const double* dalpha0, double* dalpha,
                    int* info);
+
+/* Take r observations out of a fitted model without refactoring it (no counterpart in the
+ * reference, whose only route is update_cache! on the remaining points).  dK (n0 x n0, ldk): what
+ * gpr_fit left (U in the upper triangle, K strictly below); read only, left bit for bit as it was:
+ * the old model stays usable.  idx: r HOST indices, 0-based, strictly ascending.  dy: the y of the
+ * KEPT points, (n0 - r) x nrhs (ldy).  dKout (ldo >= n0 - r) must not overlap dK; its leading
+ * (n0 - r) x (n0 - r) receives what gpr_fit on the kept points would have left (within rounding): U'
+ * in the upper triangle, K strictly below (the old entries, compacted); nothing else is written.
+ * dalpha: (n0 - r) x nrhs with leading dimension n0 - r, receives K'^{-1} y by the two sweeps of
+ * gpr_potrs_upper on dKout.  No kinds, hp or X: nothing is evaluated, so every kernel description
+ * is served.
+ * With keep the remaining indices, T = U[keep, keep] and W = U[D, keep] (entries left of a removed
+ * point's own column masked to zero), K[keep, keep] = T^T T + W^T W: U' is T after a rank-r positive
+ * update by Givens rotations (rows ascending, removed points ascending within a row, 8 removed
+ * points per pass over the triangle) -- O(n^2 r) work, no pivot can fail, hence no info.  Rows above
+ * the first removed point's 128-row block are copied; removing only the newest points is a pure
+ * copy.  Two routes (GPR_REMOVE_SWEEP) with the same arithmetic on every element: they, and two
+ * calls of one route, agree bit for bit.
+ * The context's factor cache is left valid for dKout: gpr_predict, gpr_predict_grad, gpr_mll,
+ * gpr_potrs_upper, gpr_mvn_sample, gpr_fit_append on (dKout, n0 - r, ldo) follow with no
+ * gpr_forget_factor.
+ * GPR_E_ARG for r < 1, r >= n0, nrhs < 1, ldk < n0, ldo < n0 - r, ldy < n0 - r, a NULL pointer, idx
+ * not strictly ascending or outside [0, n0), dKout overlapping dK: the message names the argument,
+ * nothing is written.  Synchronises before it returns. */
+int gpr_fit_remove(gpr_ctx_t ctx, const double* dK, int n0, int ldk, const int* idx, int r,
+                   const double* dy, int nrhs, int ldy, double* dKout, int ldo, double* dalpha);
 
 /* ---- a10/a11: posterior ------------------------------------------------------------ */
 /* Posterior at m test points from a fitted factor (dU, dwt = K^{-1} y with nrhs cols).
