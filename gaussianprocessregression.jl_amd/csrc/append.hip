@@ -290,13 +290,13 @@ __global__ __launch_bounds__(256) void append_head_kernel(const double* __restri
 // V = U^{-T} B in place (B n0 x m, ld ldb) by the single-launch sweep, 16 columns per launch
 int append_sweep(gpr_ctx* ctx, const double* dU, int n0, int ldu, double* B, int m, int ldb) {
   const int nblk = (n0 + AS_NB - 1) / AS_NB;
-  GPR_TRY(ensure_buf(ctx, &ctx->dahand, &ctx->ahand_cap, (size_t)nblk * AS_BLK));
-  int* sync = ctx->dinfo + 8;  // dinfo[8..9]: ticket / blocks done
+  GPR_TRY(ensure_buf(ctx, ctx->dahand, (size_t)nblk * AS_BLK));
+  int* sync = ctx->dinfo + INFO_SKINNY;
   const bool vec = ((uintptr_t)dU % 16) == 0 && (ldu % 2) == 0;
   for (int g0 = 0; g0 < m; g0 += AS_NC) {
     const int nc = std::min(AS_NC, m - g0);
     double* Bg = B + (size_t)g0 * ldb;
-    HIP_TRY(ctx, hipMemsetAsync(sync, 0, 2 * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(sync, 0, INFO_SKINNY_N * sizeof(int), ctx->stream));
     if (vec)
       append_fwd_sweep_kernel<true><<<nblk, AS_THREADS, 0, ctx->stream>>>(
           dU, (size_t)ldu, n0, ctx->winv, Bg, (size_t)ldb, nc, ctx->dahand, sync);
@@ -345,8 +345,8 @@ int gpr_fit_append(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, in
 
   // the block inverses of the old factor, in a winv that already has room for the new blocks (a
   // regrown one has lost its contents: the inverses are then computed afresh)
-  if (ctx->winv_cap < (size_t)((N + nb - 1) / nb) * nb * nb) {
-    ctx->fac_valid = false;
+  if (ctx->winv.cap < (size_t)((N + nb - 1) / nb) * nb * nb) {
+    ctx->fc.factor_forget_blocks();
     GPR_TRY(ensure_winv(ctx, N + N / 8, nb));
   }
   GPR_TRY(ensure_factor_inverses(ctx, dK, n0, ldk));
@@ -380,8 +380,7 @@ int gpr_fit_append(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, in
   double* Winv = nullptr;  // R^{-1} of a small append
   if (small) {
     const int nslab = (n0 + SC_SLAB - 1) / SC_SLAB;
-    GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap,
-                       (size_t)(nslab + 1) * AS_NB * AS_NB));
+    GPR_TRY(ensure_buf(ctx, ctx->dscratch, (size_t)(nslab + 1) * AS_NB * AS_NB));
     Winv = ctx->dscratch;
     double* partial = Winv + AS_NB * AS_NB;
     {
@@ -392,25 +391,17 @@ int gpr_fit_append(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, in
                                                                          (size_t)ldk);
       LAUNCH_CHECK(ctx);
     }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), st));
+    GPR_TRY(info_clear(ctx, st));
     GPR_TRY(diag_factor_block(ctx, dK, ldk, N, n0, Winv));  // (a failing pivot: n0 + its order)
-    HIP_TRY(ctx, hipMemcpyAsync(&hinfo, ctx->dinfo, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+    GPR_TRY(info_read(ctx, st, &hinfo));
   } else {
-    GemmArgs g{};
-    g.P = Kc; g.ldp = ldk;
-    g.Q = Kc; g.ldq = ldk;
-    g.C = Kn; g.ldc = ldk;
-    g.M = m; g.N = m; g.K = n0;
-    g.alpha = -1.0; g.beta = 1.0;
-    g.upper = 1;
-    GPR_TRY(launch_gemm_tn(ctx, g, TC_OTHER));
+    GPR_TRY(launch_gemm_tn(ctx, syrk_upper_args(Kc, ldk, Kn, ldk, m, n0, -1.0, 1.0), TC_OTHER));
     // (the context's factor cache now describes the sub-block; re-established below)
     GPR_TRY(potrf_core(ctx, Kn, m, ldk, &hinfo));
     if (hinfo > 0) hinfo += n0;
   }
   if (hinfo != 0) {
-    if (!small) gpr_forget_factor(ctx);
+    if (!small) ctx->fc.factor_forget();
     if (info) *info = hinfo;
     return hinfo;
   }
@@ -437,10 +428,9 @@ int gpr_fit_append(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, in
   }
   // the factor cache, extended: the block that straddles n0 and the new ones (potrs_core left
   // the cache on (dK, n0, ldk))
-  HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), st));
+  GPR_TRY(info_clear(ctx, st));
   GPR_TRY(diag_inverse_blocks(ctx, dK, ldk, N, n0 / nb));
-  ctx->fac_n = N;
-  ctx->sqinv_nb2 = 0;
+  ctx->fc.factor_extend(N);
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return 0;
 }

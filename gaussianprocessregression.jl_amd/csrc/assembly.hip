@@ -348,16 +348,15 @@ __global__ void set_identity_kernel(double* __restrict__ A, int n, size_t lda) {
   }
 }
 
-int scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double** buf,
-                 size_t* cap) {
-  GPR_TRY(ensure_buf(ctx, buf, cap, (size_t)kp.nse * kp.de * n + 1));
+int scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, DevBuf& buf) {
+  GPR_TRY(ensure_buf(ctx, buf, (size_t)kp.nse * kp.de * n + 1));
   const size_t total = (size_t)kp.nse * kp.dx * n;
   int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
   if (blocks < 1) blocks = 1;
   if (kp.nper)  // (every part 2d features wide)
-    embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 0, *buf);
+    embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 0, buf.p);
   else
-    scale_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, *buf);
+    scale_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, buf.p);
   LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -1296,9 +1295,9 @@ int gram_prepare(gpr_ctx* ctx, const KParams& kp, int S, const double* xs, int n
   const int nbB = same ? nbA : ((m + KT - 1) / KT) * (KT / 16);
   const size_t opA = (size_t)kp.nse * nbA * S * 64, opB = same ? 0 : (size_t)kp.nse * nbB * S * 64;
   const size_t nA = (size_t)kp.nse * nbA * 16, nB = same ? 0 : (size_t)kp.nse * nbB * 16;
-  GPR_TRY(ensure_buf(ctx, &ctx->dgc, &ctx->gc_cap, gram_centres_cap(kp)));
-  GPR_TRY(ensure_buf(ctx, &ctx->dgA, &ctx->gA_cap, opA + nA + (same ? opA : 0)));
-  if (!same) GPR_TRY(ensure_buf(ctx, &ctx->dgB, &ctx->gB_cap, opB + nB));
+  GPR_TRY(ensure_buf(ctx, ctx->dgc, gram_centres_cap(kp)));
+  GPR_TRY(ensure_buf(ctx, ctx->dgA, opA + nA + (same ? opA : 0)));
+  if (!same) GPR_TRY(ensure_buf(ctx, ctx->dgB, opB + nB));
   double* A = ctx->dgA;
   double* nrmA = A + opA;
   double* B = same ? nrmA + nA : ctx->dgB;
@@ -1524,9 +1523,9 @@ __global__ __launch_bounds__(256) void pair_kernel(int mode, int d, const double
 
 int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kpx, const double* dX, int n,
                          const double* dXp, int m, int same, double* dK, int ldk) {
-  if (dK == ctx->kup_ptr) ctx->kup_ptr = nullptr;  // (rebuilt in full)
+  if (ctx->fc.kup_pending(dK)) ctx->fc.kup_drop();  // (rebuilt in full)
   if (n <= 0 || (!same && m <= 0)) return 0;
-  GPR_TRY(scale_inputs(ctx, kpx, dX, n, &ctx->dxs, &ctx->xs_cap));
+  GPR_TRY(scale_inputs(ctx, kpx, dX, n, ctx->dxs));
   // everything below works on the scaled (embedded) points: its d is the feature width de, so
   // the path (compile-time S, upper-only, run-time tile) is chosen by de
   const KParams kp = kparams_features(kpx);
@@ -1548,7 +1547,7 @@ int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kpx, const double* dX, int
     DISPATCH_D(launch_sym, ctx, kp, ctx->dxs, n, dK, ldk);
     LAUNCH_CHECK(ctx);
   } else {
-    GPR_TRY(scale_inputs(ctx, kpx, dXp, m, &ctx->dxps, &ctx->xps_cap));
+    GPR_TRY(scale_inputs(ctx, kpx, dXp, m, ctx->dxps));
     TimerScope ts(ctx, TC_OTHER, 0.0);
     if (gram_enabled(ctx, kp.d) && vec_store_ok(dK, ldk))
       return kp.nse > KMAXP ? launch_gram_groups(ctx, kp, ctx->dxs, n, ctx->dxps, m, 0, dK, ldk)
@@ -1561,7 +1560,7 @@ int launch_kernel_matrix(gpr_ctx* ctx, const KParams& kpx, const double* dX, int
 
 int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kpx, const double* dX, int n,
                                     double* dK, int ldk) {
-  ctx->kup_ptr = nullptr;
+  ctx->fc.kup_drop();
   const KParams kp = kparams_features(kpx);  // (paths by the feature width de)
   // upper-only where the tile-DAG will take exactly this matrix directly (potrf_core), with
   // the Gram form (d <= 20) and one or two SquaredExp parts; the full symmetric K otherwise
@@ -1570,7 +1569,7 @@ int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kpx, const doub
                      kp.d <= GRAM_CT_MAXD && kp.nse <= 2 && !kp.mix &&
                      dag_takes_whole(ctx, n, ldk, dK) && dag_shape_ok(n, ldk, dK);
   if (!upper) return launch_kernel_matrix(ctx, kpx, dX, n, nullptr, n, 1, dK, ldk);
-  GPR_TRY(scale_inputs(ctx, kpx, dX, n, &ctx->dxs, &ctx->xs_cap));
+  GPR_TRY(scale_inputs(ctx, kpx, dX, n, ctx->dxs));
   {
     // bytes written: column c gets min(n, 128 (c / 128 + 1)) rows
     double bytes = 0.0;
@@ -1579,9 +1578,7 @@ int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kpx, const doub
     GPR_TRY(kp.nse == 1 ? launch_gram_upper_s<1>(ctx, kp, ctx->dxs, n, dK, ldk, 0)
                         : launch_gram_upper_s<2>(ctx, kp, ctx->dxs, n, dK, ldk, 0));
   }
-  ctx->kup_ptr = dK;
-  ctx->kup_n = n;
-  ctx->kup_ld = ldk;
+  ctx->fc.kup_claim(dK, n, ldk);
   return 0;
 }
 
@@ -1594,19 +1591,18 @@ int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n
   return 0;
 }
 
-int launch_embed_unit_to(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double** buf,
-                         size_t* cap) {
+int launch_embed_unit_to(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, DevBuf& buf) {
   if (!kp.nper || n <= 0) return 0;
-  GPR_TRY(ensure_buf(ctx, buf, cap, (size_t)kp.nse * kp.de * n + 1));
+  GPR_TRY(ensure_buf(ctx, buf, (size_t)kp.nse * kp.de * n + 1));
   const size_t total = (size_t)kp.nse * kp.dx * n;
   const int blocks = (int)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 4096));
-  embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 1, *buf);
+  embed_inputs_kernel<<<blocks, 256, 0, ctx->stream>>>(kp, dX, n, 1, buf.p);
   LAUNCH_CHECK(ctx);
   return 0;
 }
 
 int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n) {
-  return launch_embed_unit_to(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap);
+  return launch_embed_unit_to(ctx, kp, dX, n, ctx->dxs);
 }
 
 int launch_pair(gpr_ctx* ctx, int mode, int d, const double* xa, int na, const double* xb, int nb,
@@ -1674,7 +1670,7 @@ int gpr_kernel_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
         LAUNCH_CHECK(ctx);
         return 0;
       }
-      GPR_TRY(scale_inputs(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));
+      GPR_TRY(scale_inputs(ctx, kp, dX, n, ctx->dxs));
       int t0 = se, t1 = se;  // the part's term: parts [t0, t1]
       while (t0 > 0 && !kp_closes(kp, t0 - 1)) --t0;
       while (!kp_closes(kp, t1)) ++t1;

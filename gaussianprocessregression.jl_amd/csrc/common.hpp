@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/gpr_hip.h"
+#include "factor_cache.hpp"
 
 #define KMAXP 4   // stationary parts one fused-kernel launch handles (more: groups of KMAXP)
 
@@ -194,6 +195,25 @@ struct KParBlock {
   std::vector<double> tmp; // the description being made
 };
 
+// A device workspace of the context: grown by ensure_buf, freed by release_buf and by nothing
+// else.  Every one is listed in kWorkspaces (gpr_ctx.hip), which gpr_ctx_destroy walks.
+struct DevBuf {
+  double* p = nullptr;
+  size_t cap = 0;  // doubles
+  // (reads as the pointer it replaced -- but not through varargs: pass b.p to a "%p")
+  operator double*() const { return p; }
+};
+
+// The context's device info words (gpr_ctx::dinfo, ints)
+enum {
+  INFO_WORD = 0,     // pivot / timeout info of a factorisation or solve (info_clear, info_read)
+  INFO_POTRS = 4,    // potrs_core's sweep counters: fwd ticket/done, bwd ticket/done
+  INFO_POTRS_N = 4,
+  INFO_SKINNY = 8,   // the skinny sweeps of append.hip and remove.hip: ticket / blocks done
+  INFO_SKINNY_N = 2,
+  INFO_N = 16
+};
+
 // TC_GEMM_PIPE is kernel-level (every launch of the pipelined 2-WG/CU GEMM, whatever its call
 // site), recorded in addition to the call-site class.
 enum TimingClass {
@@ -263,8 +283,6 @@ struct gpr_ctx {
   // this context waits for it before resetting (or reallocating) the counters
   hipEvent_t dag_sync_readers = nullptr;
   bool dag_sync_readers_pending = false;
-  bool rhs_solved = false; // the last potrf_core solved its RhsSpec (not dropped by its block sizes)
-  bool gram_full = false; // the last potrf_core wrote its RhsSpec gram in full (the tile-DAG)
   int dag_gram = 1;       // K^{-1} += Z^T Z as gram tile tasks of the DAG launch (GPR_DAG_GRAM)
   int dag_solve = -1;     // solves from a finished factor as solve-only DAG launches (GPR_DAG_SOLVE; -1 auto)
   int dag_tail = 12288;  // blocked factorisations (GPR_DAG=0, ineligible sizes) hand their last
@@ -273,10 +291,7 @@ struct gpr_ctx {
   int dag_ntasks = 0, dag_nt = -1, dag_ntr = -1, dag_flags = -1;
   int* dag_sync = nullptr;
   size_t dag_sync_cap = 0;
-  double* dpadA = nullptr;  // padded copies for shapes the DAG launch does not take directly
-  size_t padA_cap = 0;
-  double* dpadB = nullptr;
-  size_t padB_cap = 0;
+  DevBuf dpadA, dpadB;  // padded copies for shapes the DAG launch does not take directly
   // rocSOLVER (dlopen'd, gpr_integrate_noise's eigendecomposition): a rocBLAS handle on this
   // context's stream, created on first use; rb_destroy releases it
   void* rb_handle = nullptr;
@@ -287,55 +302,33 @@ struct gpr_ctx {
 
   // cached inverses of the diagonal blocks of the last factor: winv[b] = U_bb^{-1}
   // (nb x nb, column-major, strictly-lower part zero), one slot per block.
-  double* winv = nullptr;
-  size_t winv_cap = 0;  // doubles
-  const double* fac_ptr = nullptr;
-  int fac_n = 0, fac_ld = 0, fac_nb = 0;
-  bool fac_valid = false;
+  DevBuf winv;
+  FactorCache fc;  // which factor winv / dsqinv belong to, and the upper-only assembly's claim
 
-  int* dinfo = nullptr;         // device info word
+  int* dinfo = nullptr;         // device info words (INFO_*)
   double* dexptab = nullptr;    // 2^(j/256), j < 256, correctly rounded (assembly exp)
-  double* dscratch = nullptr;   // generic scratch (partials, small vectors)
-  size_t scratch_cap = 0;       // doubles
+  DevBuf dscratch;              // generic scratch (partials, small vectors)
   // child contexts that run cross-validation folds concurrently (gpr_cv_batch)
   static constexpr int CV_MAX_SUB = 8;
   struct gpr_ctx* cv_sub[CV_MAX_SUB] = {};
   int cv_streams = 4;  // GPR_CV_STREAMS
-  double* dbig = nullptr;       // large scratch (Z for potri, Kpx for predict, ...)
-  size_t big_cap = 0;           // doubles
-  double* dbig2 = nullptr;
-  size_t big2_cap = 0;
-  double* dsqinv = nullptr;     // U_sq^{-1} of every outer panel square (nb2^2 per slot)
-  size_t sqinv_cap = 0;         // doubles
-  int sqinv_nb2 = 0;            // nb2 the slots were written with (0 = none valid)
-  const double* sq_ptr = nullptr;  // factor the slots belong to
-  int sq_n = 0, sq_ld = 0;
-  double* dpanel = nullptr;     // out-of-place result of the panel's rest GEMM
-  size_t panel_cap = 0;
-  double* dtrsv = nullptr;      // single-launch triangular sweep hand-off vector (n x 2)
-  size_t trsv_cap = 0;
-  double* dahand = nullptr;     // the append's skinny solve: hand-off blocks (128 x 16 per block)
-  size_t ahand_cap = 0;
-  double* drmw = nullptr;       // gpr_fit_remove: a group's W rows (8 x n'), then keep[] and idx[]
-  size_t rmw_cap = 0;
-  double* dxs = nullptr;        // per-part scaled training inputs  (nse x d x n)
-  size_t xs_cap = 0;
-  double* dxps = nullptr;       // per-part scaled second inputs    (nse x d x m)
-  size_t xps_cap = 0;
-  double* dscr_wt = nullptr;     // gpr_fit_predict: K^{-1} y when the caller passes no alpha
-  size_t scr_wt_cap = 0;
-  double* dpanel_rhs = nullptr;  // solved outer panel of the fused right-hand sides
-  size_t panel_rhs_cap = 0;
-  double* dgA = nullptr;        // Gram-assembly row operands (MFMA lane order, assembly.hip)
-  size_t gA_cap = 0;
-  double* dgB = nullptr;        // Gram-assembly column operands
-  size_t gB_cap = 0;
-  double* dgc = nullptr;        // Gram-assembly centres (nse x d)
-  size_t gc_cap = 0;
+  DevBuf dbig, dbig2;           // large scratch (Z for potri, Kpx for predict, ...)
+  DevBuf dsqinv;                // U_sq^{-1} of every outer panel square (nb2^2 per slot)
+  DevBuf dpanel;                // out-of-place result of the panel's rest GEMM
+  DevBuf dtrsv;                 // single-launch triangular sweep hand-off vector (n x 2)
+  DevBuf dahand;                // the append's skinny solve: hand-off blocks (128 x 16 per block)
+  DevBuf drmw;                  // gpr_fit_remove: a group's W rows (8 x n'), then keep[] and idx[]
+  DevBuf dxs;                   // per-part scaled training inputs  (nse x d x n)
+  DevBuf dxps;                  // per-part scaled second inputs    (nse x d x m)
+  DevBuf dscr_wt;                // gpr_fit_predict: K^{-1} y when the caller passes no alpha
+  DevBuf dpanel_rhs;             // solved outer panel of the fused right-hand sides
+  DevBuf dgA;                   // Gram-assembly row operands (MFMA lane order, assembly.hip)
+  DevBuf dgB;                   // Gram-assembly column operands
+  DevBuf dgc;                   // Gram-assembly centres (nse x d)
   // upper-only K assembly for a factorisation (assembly.hip kmat_symu_kernel): its work list
-  // (strip << 16 | segment, built once per n) and the matrix it last left without its strict
-  // lower off-diagonal tiles -- the next potrf_core on exactly that matrix has the tile-DAG
-  // write them (DAG_MIRROR), or mirrors them first on any other path
+  // (strip << 16 | segment, built once per n); the matrix it last left without its strict
+  // lower off-diagonal tiles is fc's kup claim -- the next potrf_core on exactly that matrix has
+  // the tile-DAG write them (DAG_MIRROR), or mirrors them first on any other path
   struct KupList {
     long long key = -1;  // 2 n + full
     int nitems = 0;
@@ -344,21 +337,15 @@ struct gpr_ctx {
   };
   KupList kup[4];
   unsigned long long kup_clock = 0;
-  const double* kup_ptr = nullptr;
-  int kup_n = 0, kup_ld = 0;
-  double* dagb = nullptr;       // batched tile-DAG workspace (W slots, task lists, counters)
-  size_t dagb_cap = 0;
-  double* deig = nullptr;       // eigensolver workspace (eigen.hip, tridiag.hip)
-  size_t eig_cap = 0;
-  double* ddc = nullptr;        // divide-and-conquer workspace (dstedc.hip)
-  size_t dc_cap = 0;
+  DevBuf dagb;                  // batched tile-DAG workspace (W slots, task lists, counters)
+  DevBuf deig;                  // eigensolver workspace (eigen.hip, tridiag.hip)
+  DevBuf ddc;                   // divide-and-conquer workspace (dstedc.hip)
   // its merge tables' pinned host staging buffer, re-filled only after dc_tab_ev (the previous
   // call's upload) has completed
   int* dc_tab_host = nullptr;
   size_t dc_tab_host_cap = 0;
   hipEvent_t dc_tab_ev = nullptr;
-  double* dtri = nullptr;       // the tridiagonal T between the two stages
-  size_t tri_cap = 0;
+  DevBuf dtri;                  // the tridiagonal T between the two stages
   int kbuild_upper = 1;         // GPR_KBUILD_UPPER=0: fits build the full K (mirrored tiles)
   int kbuild_exact = 0;         // GPR_KBUILD_EXACT=1: the reference's difference form for K
   int kbuild_gram_maxd = 1 << 30;  // GPR_KBUILD_GRAM_MAXD: largest d that takes the Gram form
@@ -431,8 +418,16 @@ inline int refuse_non_se(gpr_ctx* ctx, const int* kinds, int nk, const char* wha
 }
 
 // ---- workspace ------------------------------------------------------------------------
-int ensure_buf(gpr_ctx* ctx, double** p, size_t* cap, size_t need_doubles);
+int ensure_buf(gpr_ctx* ctx, DevBuf& b, size_t need_doubles);
+// the one place a workspace is freed: synchronise, free, zero, and drop every cache of ctx->fc
+// whose key points into the freed range
+// (synced: the caller has synchronised the stream already -- several buffers in a row, one wait)
+int release_buf(gpr_ctx* ctx, DevBuf& b, bool synced = false);
 int ensure_winv(gpr_ctx* ctx, int n, int nb);
+// ---- info word ------------------------------------------------------------------------
+// clear INFO_WORD in stream order; copy it back and synchronise the stream
+int info_clear(gpr_ctx* ctx, hipStream_t st);
+int info_read(gpr_ctx* ctx, hipStream_t st, int* hinfo);
 
 // ---- timing ---------------------------------------------------------------------------
 struct TimerScope {
@@ -493,8 +488,7 @@ int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n
 // per-point table
 int launch_embed_unit(gpr_ctx* ctx, const KParams& kp, const double* dX, int n);
 // the same into *buf (grown to nse x 2d x n doubles): the posterior gradient's training and test points
-int launch_embed_unit_to(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double** buf,
-                         size_t* cap);
+int launch_embed_unit_to(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, DevBuf& buf);
 int launch_pair(gpr_ctx* ctx, int mode, int d, const double* xa, int na, const double* xb, int nb,
                 double s2, double* out, size_t sa, size_t sb);
 int launch_set_identity(gpr_ctx* ctx, double* A, int n, int lda);
@@ -512,6 +506,9 @@ struct RhsSpec {
   // (X_s^T X_s of each solved panel, upper; potrf_core zeroes it first; the caller mirrors)
   double* gram;
   int ldg;
+  // results, written by potrf_core
+  bool solved = false;     // B was solved (else dropped by the block sizes: the caller solves it)
+  bool gram_full = false;  // gram was written in full (the tile-DAG; else the caller mirrors)
 };
 // one-launch tile-DAG factorisation (+ B <- U^{-T} B); 1 = shape not eligible, 0 = launched
 // DAG_GRAM (with DAG_LOWER, B = the identity's Z = U^{-T}): also G = Z^T Z (every tile)
@@ -529,8 +526,21 @@ int launch_potrf_dag_batch(gpr_ctx* ctx, double* dA, size_t strA, int n, int lda
                            size_t strB, int nrhs, int ldb, int nbatch, int* info_out);
 int launch_potrf_dag_padded(gpr_ctx* ctx, double* dA, int n, int lda, double* dB, int nrhs,
                             int ldb);
-int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info,
-               const RhsSpec* rhs = nullptr);
+int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, RhsSpec* spec = nullptr);
+// the upper-triangle product C = beta C + alpha P^T P (P: K x n, ld ldp) as launch_gemm_tn takes it
+inline GemmArgs syrk_upper_args(const double* P, int ldp, double* C, int ldc, int n, int K,
+                                double alpha, double beta) {
+  GemmArgs g{};
+  g.P = P; g.ldp = ldp;
+  g.Q = P; g.ldq = ldp;
+  g.C = C; g.ldc = ldc;
+  g.M = n; g.N = n; g.K = K;
+  g.alpha = alpha; g.beta = beta;
+  g.upper = 1;
+  return g;
+}
+// dst (ld n) <- the n x nrhs columns of src (ld lds), device to device on ctx->stream
+int copy_columns(gpr_ctx* ctx, double* dst, int n, const double* src, int lds, int nrhs);
 int ensure_factor_inverses(gpr_ctx* ctx, const double* dU, int n, int ldu);
 // the diagonal-block kernels on their own (potrf.hip): factor the block at kglob of A in place
 // (inverse into winv; a failing pivot: kglob + its order in ctx->dinfo), and ctx->winv's slots

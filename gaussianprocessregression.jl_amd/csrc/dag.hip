@@ -927,8 +927,8 @@ int launch_potrf_dag_padded(gpr_ctx* ctx, double* dA, int n, int lda, double* dB
                             int ldb) {
   const int n2 = (n + 15) / 16 * 16;
   hipStream_t st = ctx->stream;
-  if (ensure_buf(ctx, &ctx->dpadA, &ctx->padA_cap, (size_t)n2 * n2) != 0 ||
-      (dB && ensure_buf(ctx, &ctx->dpadB, &ctx->padB_cap, (size_t)n2 * nrhs) != 0)) {
+  if (ensure_buf(ctx, ctx->dpadA, (size_t)n2 * n2) != 0 ||
+      (dB && ensure_buf(ctx, ctx->dpadB, (size_t)n2 * nrhs) != 0)) {
     ctx->err.clear();
     (void)hipGetLastError();  // do not leave the allocation failure for the next launch check
     return 1;
@@ -1135,7 +1135,7 @@ int launch_potrf_dag_batch(gpr_ctx* ctx, double* dA, size_t strA, int n, int lda
   // workspace (doubles): W slots | tasks | tbatch | sync | info (ints packed two per double)
   const size_t nW = (size_t)nbatch * nt * DT * DT;
   const size_t nI = (size_t)ntasks * 2 + (size_t)nbatch * strS + (size_t)nbatch;
-  GPR_TRY(ensure_buf(ctx, &ctx->dagb, &ctx->dagb_cap, nW + (nI + 1) / 2 + 1));
+  GPR_TRY(ensure_buf(ctx, ctx->dagb, nW + (nI + 1) / 2 + 1));
   double* W = ctx->dagb;
   unsigned* dtasks = reinterpret_cast<unsigned*>(W + nW);
   int* dtb = reinterpret_cast<int*>(dtasks + ntasks);

@@ -613,7 +613,7 @@ int tridiag_eig_apply(gpr_ctx* ctx, const double* dd, const double* de, int n, d
     while (kp < off[dpt].kmax) kp <<= 1;
     if (kp > DC_LDS_SORT) gsort_cap = std::max(gsort_cap, (size_t)off[dpt].nmerge * kp);
   }
-  GPR_TRY(ensure_buf(ctx, &ctx->ddc, &ctx->dc_cap, 2 * nX + nvec + ntab + gsort_cap + (gsort_cap + 1) / 2));
+  GPR_TRY(ensure_buf(ctx, ctx->ddc, 2 * nX + nvec + ntab + gsort_cap + (gsort_cap + 1) / 2));
   double* X = ctx->ddc;
   double* Xt = X + nX;
   double* v = Xt + nX;

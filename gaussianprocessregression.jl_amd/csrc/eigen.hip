@@ -492,7 +492,7 @@ static int jacobi_eig_apply(gpr_ctx* ctx, const double* dA, int n, int lda, doub
   const int ntiles = np * (np + 1) / 2;
   // workspace: W (n2 x n2), Bp (n2 x m), R (np x 64 x 64), rotation counter
   const size_t need = (size_t)n2 * n2 + (size_t)n2 * std::max(m, 1) + (size_t)np * ES * ES + 2 + np;
-  GPR_TRY(ensure_buf(ctx, &ctx->deig, &ctx->eig_cap, need));
+  GPR_TRY(ensure_buf(ctx, ctx->deig, need));
   double* W = ctx->deig;
   double* Bp = W + (size_t)n2 * n2;
   double* Rb = Bp + (size_t)n2 * std::max(m, 1);
@@ -545,7 +545,7 @@ int sym_eig_apply(gpr_ctx* ctx, const double* dA, int n, int lda, double* dB, in
     return 0;
   }
   if (method != 2 && sym_tridiag_ok(n) && tridiag_eig_ok(n)) {
-    GPR_TRY(ensure_buf(ctx, &ctx->dtri, &ctx->tri_cap, 2 * (size_t)n + 2));
+    GPR_TRY(ensure_buf(ctx, ctx->dtri, 2 * (size_t)n + 2));
     double* d = ctx->dtri;
     double* e = d + n + 1;
     const int rc = sym_tridiag(ctx, dA, n, lda, dB, m, ldb, d, e);

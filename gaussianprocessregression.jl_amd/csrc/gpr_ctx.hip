@@ -19,26 +19,51 @@ int set_err(gpr_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
-int ensure_buf(gpr_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (*cap >= need && *p) return 0;
-  if (*p) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-  }
+int release_buf(gpr_ctx* ctx, DevBuf& b, bool synced) {
+  if (!b.p) return 0;
+  // (a stream that cannot be synchronised may still be using the buffer: it is kept, and the
+  // error returned, as ensure_buf's regrow always did)
+  if (!synced) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipFree(b.p));
+  ctx->fc.release_range(b.p, b.cap);
+  b = DevBuf{};
+  return 0;
+}
+
+int ensure_buf(gpr_ctx* ctx, DevBuf& b, size_t need) {
+  if (b.cap >= need && b.p) return 0;
+  GPR_TRY(release_buf(ctx, b));
   if (need == 0) need = 1;
-  if (hipMalloc((void**)p, need * sizeof(double)) != hipSuccess) {
-    *p = nullptr;
+  if (hipMalloc((void**)&b.p, need * sizeof(double)) != hipSuccess) {
+    b.p = nullptr;
     return set_err(ctx, GPR_E_NOMEM, "hipMalloc of %zu bytes failed", need * sizeof(double));
   }
-  *cap = need;
+  b.cap = need;
   return 0;
 }
 
 int ensure_winv(gpr_ctx* ctx, int n, int nb) {
   size_t nblk = (size_t)((n + nb - 1) / nb);
-  return ensure_buf(ctx, &ctx->winv, &ctx->winv_cap, nblk * nb * nb);
+  return ensure_buf(ctx, ctx->winv, nblk * nb * nb);
+}
+
+int info_clear(gpr_ctx* ctx, hipStream_t st) {
+  HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo + INFO_WORD, 0, sizeof(int), st));
+  return 0;
+}
+
+int info_read(gpr_ctx* ctx, hipStream_t st, int* hinfo) {
+  HIP_TRY(ctx, hipMemcpyAsync(hinfo, ctx->dinfo + INFO_WORD, sizeof(int), hipMemcpyDeviceToHost,
+                              st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+
+int copy_columns(gpr_ctx* ctx, double* dst, int n, const double* src, int lds, int nrhs) {
+  HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)n * sizeof(double), src, (size_t)lds * sizeof(double),
+                                (size_t)n * sizeof(double), nrhs, hipMemcpyDeviceToDevice,
+                                ctx->stream));
+  return 0;
 }
 
 // ---- timing ----------------------------------------------------------------------------
@@ -298,6 +323,15 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
   }
 }
 
+// Every device workspace of a context; gpr_ctx_destroy releases exactly these.
+DevBuf gpr_ctx::*const kWorkspaces[] = {
+    &gpr_ctx::winv,   &gpr_ctx::dscratch, &gpr_ctx::dbig,       &gpr_ctx::dbig2, &gpr_ctx::dsqinv,
+    &gpr_ctx::dpanel, &gpr_ctx::dtrsv,    &gpr_ctx::dahand,     &gpr_ctx::drmw,  &gpr_ctx::dxs,
+    &gpr_ctx::dxps,   &gpr_ctx::dscr_wt,  &gpr_ctx::dpanel_rhs, &gpr_ctx::dgA,   &gpr_ctx::dgB,
+    &gpr_ctx::dgc,    &gpr_ctx::dpadA,    &gpr_ctx::dpadB,      &gpr_ctx::dagb,  &gpr_ctx::deig,
+    &gpr_ctx::ddc,    &gpr_ctx::dtri,
+};
+
 const Knob* knob_find(const char* name) {
   if (!name) return nullptr;
   for (const Knob& k : kKnobs)
@@ -324,14 +358,15 @@ int gpr_ctx_create(int device, void* stream, gpr_ctx_t* out) {
   gpr_ctx* ctx = new gpr_ctx();
   ctx->device = device;
   if (hipSetDevice(device) != hipSuccess) {
-    delete ctx;
+    gpr_ctx_destroy(ctx);
     return GPR_E_HIP;
   }
   if (stream) {
     ctx->stream = (hipStream_t)stream;
   } else {
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete ctx;
+      ctx->stream = nullptr;
+      gpr_ctx_destroy(ctx);
       return GPR_E_HIP;
     }
     ctx->own_stream = true;
@@ -341,10 +376,14 @@ int gpr_ctx_create(int device, void* stream, gpr_ctx_t* out) {
   // (diag factor + panel TRSM) must win CUs over the big trailing SYRK it overlaps
   int prio_lo = 0, prio_hi = 0;
   hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->srhs, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->ssq, hipStreamNonBlocking) != hipSuccess) {
-    delete ctx;
+  if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess)
+    ctx->stream2 = nullptr;
+  if (ctx->stream2 && hipStreamCreateWithFlags(&ctx->srhs, hipStreamNonBlocking) != hipSuccess)
+    ctx->srhs = nullptr;
+  if (ctx->srhs && hipStreamCreateWithFlags(&ctx->ssq, hipStreamNonBlocking) != hipSuccess)
+    ctx->ssq = nullptr;
+  if (!ctx->ssq) {
+    gpr_ctx_destroy(ctx);
     return GPR_E_HIP;
   }
   // Concurrent child contexts of cv_batch / integrate_noise: each drives its own stream, so
@@ -357,18 +396,19 @@ int gpr_ctx_create(int device, void* stream, gpr_ctx_t* out) {
   // the documented knobs (include/gpr_hip.h), read once here; gpr_set_knob changes them
   for (const Knob& k : kKnobs)
     if (const char* e = getenv(k.name)) knob_set(ctx, k, atof(e));
-  if (hipMalloc((void**)&ctx->dinfo, 64) != hipSuccess) {
-    delete ctx;
+  if (hipMalloc((void**)&ctx->dinfo, INFO_N * sizeof(int)) != hipSuccess) {
+    ctx->dinfo = nullptr;
+    gpr_ctx_destroy(ctx);
     return GPR_E_NOMEM;
   }
   {
     // 2^(j/256) in extended precision, rounded once to double (assembly kexp_neg table)
     double tab[256];
     for (int j = 0; j < 256; ++j) tab[j] = (double)exp2l((long double)j / 256.0L);
-    if (hipMalloc((void**)&ctx->dexptab, sizeof tab) != hipSuccess ||
+    if (hipMalloc((void**)&ctx->dexptab, sizeof tab) != hipSuccess) ctx->dexptab = nullptr;
+    if (!ctx->dexptab ||
         hipMemcpy(ctx->dexptab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
-      hipFree(ctx->dinfo);
-      delete ctx;
+      gpr_ctx_destroy(ctx);
       return GPR_E_NOMEM;
     }
   }
@@ -376,10 +416,11 @@ int gpr_ctx_create(int device, void* stream, gpr_ctx_t* out) {
   return 0;
 }
 
+// (also of a half-built context: gpr_ctx_create's failure paths end here)
 int gpr_ctx_destroy(gpr_ctx_t ctx) {
   if (!ctx) return 0;
   for (auto* sub : ctx->cv_sub) gpr_ctx_destroy(sub);
-  hipStreamSynchronize(ctx->stream);
+  if (ctx->stream) hipStreamSynchronize(ctx->stream);
   if (ctx->dag_sync_readers) {  // a hook's readers of dag_sync (freed below)
     hipEventSynchronize(ctx->dag_sync_readers);
     hipEventDestroy(ctx->dag_sync_readers);
@@ -390,41 +431,20 @@ int gpr_ctx_destroy(gpr_ctx_t ctx) {
   if (ctx->stream2) hipStreamDestroy(ctx->stream2);
   if (ctx->srhs) hipStreamDestroy(ctx->srhs);
   if (ctx->ssq) hipStreamDestroy(ctx->ssq);
-  if (ctx->dpanel_rhs) hipFree(ctx->dpanel_rhs);
-  if (ctx->dscr_wt) hipFree(ctx->dscr_wt);
+  for (auto w : kWorkspaces) (void)release_buf(ctx, ctx->*w, /*synced=*/true);
   if (ctx->dag_tasks) hipFree(ctx->dag_tasks);
   if (ctx->dag_sync) hipFree(ctx->dag_sync);
-  if (ctx->dpadA) hipFree(ctx->dpadA);
-  if (ctx->dpadB) hipFree(ctx->dpadB);
   if (ctx->rb_handle && ctx->rb_destroy) ctx->rb_destroy(ctx->rb_handle);
-  if (ctx->winv) hipFree(ctx->winv);
   if (ctx->dinfo) hipFree(ctx->dinfo);
   if (ctx->dexptab) hipFree(ctx->dexptab);
-  if (ctx->dscratch) hipFree(ctx->dscratch);
-  if (ctx->dbig) hipFree(ctx->dbig);
-  if (ctx->dbig2) hipFree(ctx->dbig2);
-  if (ctx->dtrsv) hipFree(ctx->dtrsv);
-  if (ctx->dahand) hipFree(ctx->dahand);
-  if (ctx->drmw) hipFree(ctx->drmw);
-  if (ctx->dsqinv) hipFree(ctx->dsqinv);
-  if (ctx->dpanel) hipFree(ctx->dpanel);
-  if (ctx->dxs) hipFree(ctx->dxs);
-  if (ctx->dxps) hipFree(ctx->dxps);
-  if (ctx->dgA) hipFree(ctx->dgA);
-  if (ctx->dgB) hipFree(ctx->dgB);
-  if (ctx->dgc) hipFree(ctx->dgc);
   if (ctx->kpar.dev) hipFree(ctx->kpar.dev);
   if (ctx->kpar.host) hipHostFree(ctx->kpar.host);
   for (auto e : ctx->kpar.ev)
     if (e) hipEventDestroy(e);
   for (auto& e : ctx->kup)
     if (e.d) hipFree(e.d);
-  if (ctx->deig) hipFree(ctx->deig);
-  if (ctx->ddc) hipFree(ctx->ddc);
   if (ctx->dc_tab_ev) hipEventDestroy(ctx->dc_tab_ev);
   if (ctx->dc_tab_host) hipHostFree(ctx->dc_tab_host);
-  if (ctx->dtri) hipFree(ctx->dtri);
-  if (ctx->dagb) hipFree(ctx->dagb);
   if (ctx->own_stream) hipStreamDestroy(ctx->stream);
   delete ctx;
   return 0;
@@ -468,7 +488,7 @@ int gpr_set_block(gpr_ctx_t ctx, int nb) {
   if (nb != 64 && nb != 128) return set_err(ctx, GPR_E_ARG, "nb must be 64 or 128 (got %d)", nb);
   ctx->nb = nb;
   if (ctx->nb2 % nb) ctx->nb2 = 4 * nb;
-  ctx->fac_valid = false;
+  ctx->fc.factor_forget_blocks();
   return 0;
 }
 
@@ -498,10 +518,7 @@ int gpr_get_knob(gpr_ctx_t ctx, const char* name, double* value) {
 }
 
 int gpr_forget_factor(gpr_ctx_t ctx) {
-  ctx->fac_valid = false;
-  ctx->fac_ptr = nullptr;
-  ctx->sqinv_nb2 = 0;
-  ctx->sq_ptr = nullptr;
+  ctx->fc.factor_forget();
   return 0;
 }
 

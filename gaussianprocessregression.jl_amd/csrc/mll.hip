@@ -543,7 +543,7 @@ extern "C" {
 int gpr_mll(gpr_ctx_t ctx, const double* dU, int n, int ldu, const double* dy,
             const double* dalpha, double* out) {
   if (n <= 0 || ldu < n || !dU || !dy || !dalpha || !out) return set_err(ctx, GPR_E_ARG, "bad args");
-  GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, 64));
+  GPR_TRY(ensure_buf(ctx, ctx->dscratch, 64));
   mll_terms_kernel<<<1, 1024, 0, ctx->stream>>>(dU, (size_t)ldu, n, dy, dalpha, ctx->dscratch);
   LAUNCH_CHECK(ctx);
   double h[2];
@@ -564,7 +564,7 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   const long long nblk = (long long)nt * (nt + 1) / 2;
   // per stationary part its hp width (d + 1; Periodic 2d + 1), then the WhiteNoise slot
   const int nslot = kp.nse * (d + 1) + kp.nper * d + 1;
-  GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, (size_t)nblk * nslot + nslot + 64));
+  GPR_TRY(ensure_buf(ctx, ctx->dscratch, (size_t)nblk * nslot + nslot + 64));
   double* partial = ctx->dscratch;
   double* sums = ctx->dscratch + (size_t)nblk * nslot;
   {

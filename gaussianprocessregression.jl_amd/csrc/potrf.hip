@@ -1067,7 +1067,7 @@ extern "C" int gpr_debug_chain_kernels(gpr_ctx_t ctx, double* A, int lda, int n,
   hipEventCreate(&e0);
   hipEventCreate(&e1);
   ctx->ls = ctx->stream;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), ctx->stream));
+  GPR_TRY(info_clear(ctx, ctx->stream));
   hipEventRecord(e0, ctx->stream);
   for (int r = 0; r < reps; ++r) {
     const int j = 128 * r;
@@ -1103,23 +1103,24 @@ extern "C" int gpr_debug_chain_kernels(gpr_ctx_t ctx, double* A, int lda, int n,
 //   srhs (rhs, optional): wait panel_s final; U_sq_s^{-1}; solve outer block s of B and update
 //                         the rows below (rhs_panel_step) -- the triangular solve rides in the
 //                         bubbles of the lookahead chain instead of running after the factor.
-int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpec* rhs) {
+int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, RhsSpec* spec) {
   const int nb = ctx->nb;
   const int nb2 = std::max(nb, (ctx->nb2 / nb) * nb);
-  ctx->fac_valid = false;
-  ctx->sqinv_nb2 = 0;
+  ctx->fc.factor_forget();
   // dA as the upper-only K assembly left it (launch_kernel_matrix_for_factor): its strict lower
   // off-diagonal tiles are written by the tile-DAG launch (DAG_MIRROR) or, on any other path,
   // mirrored here before the factorisation overwrites the upper triangle
-  bool mirror = ctx->kup_ptr == dA && ctx->kup_n == n && ctx->kup_ld == lda;
-  ctx->kup_ptr = nullptr;
+  bool mirror = ctx->fc.kup_take(dA, n, lda);
   GPR_TRY(ensure_winv(ctx, n, nb));
+  const RhsSpec* rhs = spec;
   if (rhs && (nb != 128 || nb2 > 2048 || !ctx->srhs || rhs->nrhs <= 0)) rhs = nullptr;
-  ctx->rhs_solved = rhs != nullptr;  // (callers solve a dropped right-hand side afterwards)
+  if (spec) {
+    spec->solved = rhs != nullptr;  // (callers solve a dropped right-hand side afterwards)
+    spec->gram_full = false;
+  }
   if (rhs) {
-    GPR_TRY(ensure_buf(ctx, &ctx->dsqinv, &ctx->sqinv_cap,
-                       (size_t)((n + nb2 - 1) / nb2) * nb2 * nb2));
-    GPR_TRY(ensure_buf(ctx, &ctx->dpanel_rhs, &ctx->panel_rhs_cap, (size_t)nb2 * rhs->nrhs));
+    GPR_TRY(ensure_buf(ctx, ctx->dsqinv, (size_t)((n + nb2 - 1) / nb2) * nb2 * nb2));
+    GPR_TRY(ensure_buf(ctx, ctx->dpanel_rhs, (size_t)nb2 * rhs->nrhs));
   }
   // a gram (K^{-1} += Z^T Z) rides in the DAG launch for the identity's Z only
   const bool dag_rhs_ok = !rhs || ((!rhs->lower_rhs || rhs->nrhs == n) &&
@@ -1127,7 +1128,7 @@ int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpe
   if (dag_takes_whole(ctx, n, lda, dA) && dag_rhs_ok) {
     // one persistent launch: tiles handed between workgroups by progress counters; shapes the
     // launch does not take directly go through a padded copy
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), ctx->stream));
+    GPR_TRY(info_clear(ctx, ctx->stream));
     int rc = 1;
     if (dag_shape_ok(n, lda, dA))  // (1 = B's layout not taken directly either)
       rc = launch_potrf_dag(ctx, dA, n, lda, rhs ? rhs->B : nullptr, rhs ? rhs->nrhs : 0,
@@ -1145,33 +1146,24 @@ int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpe
       rc = launch_potrf_dag_padded(ctx, dA, n, lda, rhs ? rhs->B : nullptr, rhs ? rhs->nrhs : 0,
                                    rhs ? rhs->ldb : 0);
     if (rc < 0) return rc;
-    ctx->gram_full = rc == 0 && rhs && rhs->gram;  // (the DAG wrote every tile of it)
     if (rc == 0) {
+      if (rhs && rhs->gram) spec->gram_full = true;  // (the DAG wrote every tile of it)
       int hinfo = 0;
-      HIP_TRY(ctx, hipMemcpyAsync(&hinfo, ctx->dinfo, sizeof(int), hipMemcpyDeviceToHost,
-                                  ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      GPR_TRY(info_read(ctx, ctx->stream, &hinfo));
       if (hinfo < 0)
         return set_err(ctx, GPR_E_HIP, "tile-DAG factorisation: a dependency wait timed out");
       if (info) *info = hinfo;
-      if (hinfo == 0) {
-        ctx->fac_valid = true;
-        ctx->fac_ptr = dA;
-        ctx->fac_n = n;
-        ctx->fac_ld = lda;
-        ctx->fac_nb = nb;
-      }
+      if (hinfo == 0) ctx->fc.factor_adopt(dA, n, lda, nb);
       return 0;
     }
   }
   if (mirror) GPR_TRY(launch_mirror_upper(ctx, dA, n, lda));
   hipStream_t user = ctx->stream;
-  ctx->gram_full = false;
   if (rhs && rhs->gram)  // accumulated panel by panel below (upper; the caller mirrors)
     HIP_TRY(ctx, hipMemset2DAsync(rhs->gram, (size_t)rhs->ldg * sizeof(double), 0,
                                   (size_t)n * sizeof(double), n, user));
   hipStream_t s0 = ctx->stream, s1 = ctx->stream2;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), user));
+  GPR_TRY(info_clear(ctx, user));
   size_t ev = 0;
   ctx->ev_next = 1000;  // events of the diag hops use a separate index range
   hipEvent_t e0 = sync_event(ctx, ev++);
@@ -1209,13 +1201,8 @@ int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpe
     if (!rhs->gram) return 0;
     // rows [k, kend) of the solved B are final: gram(0:kend, 0:kend) += B_s^T B_s (upper)
     const int kend = std::min(n, k + nb2);
-    GemmArgs g{};
-    g.P = rhs->B + k; g.ldp = rhs->ldb;
-    g.Q = rhs->B + k; g.ldq = rhs->ldb;
-    g.C = rhs->gram; g.ldc = rhs->ldg;
-    g.M = kend; g.N = kend; g.K = kend - k;
-    g.alpha = 1.0; g.beta = 1.0;
-    g.upper = 1;
+    GemmArgs g =
+        syrk_upper_args(rhs->B + k, rhs->ldb, rhs->gram, rhs->ldg, kend, kend - k, 1.0, 1.0);
     g.info = ctx->dinfo;
     return launch_gemm_tn(ctx, g, TC_TRSM_GEMM);
   };
@@ -1233,13 +1220,9 @@ int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpe
     if (tail_ok && n - kend <= ctx->dag_tail) {
       ctx->ls = s0;
       if (hipStreamWaitEvent(s0, ev_p, 0) != hipSuccess) { rc = GPR_E_HIP; break; }
-      GemmArgs b{};
-      b.P = dA + k + (size_t)kend * lda; b.ldp = lda;
-      b.Q = b.P; b.ldq = lda;
-      b.C = dA + kend + (size_t)kend * lda; b.ldc = lda;
-      b.M = n - kend; b.N = n - kend; b.K = kend - k;
-      b.alpha = -1.0; b.beta = 1.0;
-      b.upper = 1;
+      GemmArgs b = syrk_upper_args(dA + k + (size_t)kend * lda, lda,
+                                   dA + kend + (size_t)kend * lda, lda, n - kend, kend - k,
+                                   -1.0, 1.0);
       b.info = ctx->dinfo;
       if ((rc = launch_gemm_tn(ctx, b, TC_SYRK))) break;
       rc = launch_potrf_dag(ctx, dA + kend + (size_t)kend * lda, n - kend, lda, nullptr, 0, 0,
@@ -1274,13 +1257,8 @@ int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpe
       // b_s: the upper trailing matrix in one launch (round 1's split into column bands, to
       // give the lookahead stream dispatch slots in between, measured no faster)
       const int R = n - rest0;
-      GemmArgs b{};
-      b.P = dA + k + (size_t)rest0 * lda; b.ldp = lda;
-      b.Q = dA + k + (size_t)rest0 * lda; b.ldq = lda;
-      b.C = dA + rest0 + (size_t)rest0 * lda; b.ldc = lda;
-      b.M = R; b.N = R; b.K = nb2;
-      b.alpha = -1.0; b.beta = 1.0;
-      b.upper = 1;
+      GemmArgs b = syrk_upper_args(dA + k + (size_t)rest0 * lda, lda,
+                                   dA + rest0 + (size_t)rest0 * lda, lda, R, nb2, -1.0, 1.0);
       b.info = ctx->dinfo;
       rc = launch_gemm_tn(ctx, b, TC_SYRK);
       if (rc) break;
@@ -1311,41 +1289,23 @@ int potrf_core(gpr_ctx* ctx, double* dA, int n, int lda, int* info, const RhsSpe
   }
   if (rc) return rc;
   int hinfo = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&hinfo, ctx->dinfo, sizeof(int), hipMemcpyDeviceToHost, user));
-  HIP_TRY(ctx, hipStreamSynchronize(user));
+  GPR_TRY(info_read(ctx, user, &hinfo));
   if (tail_done && hinfo < 0)
     return set_err(ctx, GPR_E_HIP, "tile-DAG factorisation: a dependency wait timed out");
   if (info) *info = hinfo;
-  if (hinfo == 0 && rhs) {
-    ctx->sqinv_nb2 = nb2;
-    ctx->sq_ptr = dA;
-    ctx->sq_n = n;
-    ctx->sq_ld = lda;
-  }
-  if (hinfo == 0) {
-    ctx->fac_valid = true;
-    ctx->fac_ptr = dA;
-    ctx->fac_n = n;
-    ctx->fac_ld = lda;
-    ctx->fac_nb = nb;
-  }
+  if (hinfo == 0 && rhs) ctx->fc.sq_adopt(dA, n, lda, nb2);
+  if (hinfo == 0) ctx->fc.factor_adopt(dA, n, lda, nb);
   return 0;
 }
 
 int ensure_factor_inverses(gpr_ctx* ctx, const double* dU, int n, int ldu) {
-  if (ctx->fac_valid && ctx->fac_ptr == dU && ctx->fac_n == n && ctx->fac_ld == ldu &&
-      ctx->fac_nb == ctx->nb)
-    return 0;
   const int nb = ctx->nb;
+  if (ctx->fc.factor_known(dU, n, ldu, nb)) return 0;
   GPR_TRY(ensure_winv(ctx, n, nb));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), ctx->stream));
+  GPR_TRY(info_clear(ctx, ctx->stream));
   const int nblk = (n + nb - 1) / nb;
   GPR_TRY(launch_diag(ctx, const_cast<double*>(dU), ldu, n, 0, ctx->winv, 0, nblk));
-  ctx->fac_valid = true;
-  ctx->fac_ptr = dU;
-  ctx->fac_n = n;
-  ctx->fac_ld = ldu;
-  ctx->fac_nb = nb;
+  ctx->fc.factor_adopt(dU, n, ldu, nb);
   return 0;
 }
 
@@ -1356,19 +1316,16 @@ int ensure_sq_inverses(gpr_ctx* ctx, const double* dU, int n, int ldu) {
   const int nb2 = std::max(NB, (ctx->nb2 / NB) * NB);
   if (ctx->nb != NB || nb2 > 2048) return 0;
   GPR_TRY(ensure_factor_inverses(ctx, dU, n, ldu));
-  if (ctx->sqinv_nb2 == nb2 && ctx->sq_ptr == dU && ctx->sq_n == n && ctx->sq_ld == ldu) return 1;
+  if (ctx->fc.sq_known(dU, n, ldu, nb2)) return 1;
   const int np = (n + nb2 - 1) / nb2;
-  GPR_TRY(ensure_buf(ctx, &ctx->dsqinv, &ctx->sqinv_cap, (size_t)np * nb2 * nb2));
+  GPR_TRY(ensure_buf(ctx, ctx->dsqinv, (size_t)np * nb2 * nb2));
   {
     TimerScope ts(ctx, TC_OTHER, 0.0);
     sqinv_kernel<<<dim3(np, nb2 / NB), 256, 0, ctx->stream>>>(dU, (size_t)ldu, n, nb2, 0,
                                                               ctx->winv, ctx->dsqinv);
     LAUNCH_CHECK(ctx);
   }
-  ctx->sqinv_nb2 = nb2;
-  ctx->sq_ptr = dU;
-  ctx->sq_n = n;
-  ctx->sq_ld = ldu;
+  ctx->fc.sq_adopt(dU, n, ldu, nb2);
   return 1;
 }
 
@@ -1387,11 +1344,11 @@ static int trsm_ut_sq(gpr_ctx* ctx, const double* dU, int n, int ldu, double* dB
   // (B_rest -= U_s,rest^T X_s, K = nb2), then X_s copied back into B.  A lookahead stream for
   // the next panel's solve measured no faster (the big update loses to the co-running
   // kernels what the overlap gains) and was dropped.
-  const int nb2 = ctx->sqinv_nb2;
+  const int nb2 = ctx->fc.sq_nb2();
   hipStream_t s0 = ctx->stream;
   ctx->ls = s0;
   auto cols = [&](int kend) { return lower_rhs ? std::min(nrhs, kend) : nrhs; };
-  GPR_TRY(ensure_buf(ctx, &ctx->dpanel, &ctx->panel_cap, (size_t)nb2 * nrhs));
+  GPR_TRY(ensure_buf(ctx, ctx->dpanel, (size_t)nb2 * nrhs));
   for (int k = 0; k < n; k += nb2) {
     const int kw = std::min(nb2, n - k), kend = k + kw;
     const int nc = cols(kend);  // lower_rhs: columns >= kend of B_s are still zero
@@ -1447,15 +1404,13 @@ int trsm_ut_core(gpr_ctx* ctx, const double* dU, int n, int ldu, double* dB, int
     // The read-back synchronises the host once per solve: for C5's variance rows that is one
     // sync per 32-row batch of ~0.5 s of solve, i.e. the next batch's factor build (tens of
     // microseconds) is no longer hidden behind this one -- < 0.01 % of the job.
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dinfo, 0, sizeof(int), ctx->stream));
+    GPR_TRY(info_clear(ctx, ctx->stream));
     const int rc = launch_potrf_dag(ctx, const_cast<double*>(dU), n, ldu, dB, nrhs, ldb, 0,
                                     ctx->stream, DAG_SOLVE | (lower_rhs ? DAG_LOWER : 0));
     if (rc < 0) return rc;
     if (rc == 0) {
       int hinfo = 0;
-      HIP_TRY(ctx, hipMemcpyAsync(&hinfo, ctx->dinfo, sizeof(int), hipMemcpyDeviceToHost,
-                                  ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      GPR_TRY(info_read(ctx, ctx->stream, &hinfo));
       if (hinfo != 0)
         return set_err(ctx, GPR_E_HIP, "tile-DAG solve: a dependency wait timed out (info %d)",
                        hinfo);
@@ -1527,12 +1482,12 @@ int potrs_core(gpr_ctx* ctx, const double* dU, int n, int ldu, double* dB, int n
   const int nb = ctx->nb;
   const int nblk = (n + nb - 1) / nb;
   if (nb == SW_NB) {
-    GPR_TRY(ensure_buf(ctx, &ctx->dtrsv, &ctx->trsv_cap, (size_t)n * 2));
-    int* sync = ctx->dinfo + 4;  // dinfo[4..7]: fwd ticket/done, bwd ticket/done
+    GPR_TRY(ensure_buf(ctx, ctx->dtrsv, (size_t)n * 2));
+    int* sync = ctx->dinfo + INFO_POTRS;
     for (int c0 = 0; c0 < nrhs; c0 += 2) {
       const int nc = std::min(2, nrhs - c0);
       double* B = dB + (size_t)c0 * ldb;
-      HIP_TRY(ctx, hipMemsetAsync(sync, 0, 4 * sizeof(int), ctx->stream));
+      HIP_TRY(ctx, hipMemsetAsync(sync, 0, INFO_POTRS_N * sizeof(int), ctx->stream));
       TimerScope ts(ctx, TC_OTHER, 0.0);
       if (nc == 1)
         launch_sweeps<1>(ctx, dU, ldu, n, B, ldb, sync, forward, backward);
@@ -1608,7 +1563,7 @@ int gpr_trsm_upper_trans(gpr_ctx_t ctx, const double* dU, int n, int ldu, double
 
 int gpr_potri_upper(gpr_ctx_t ctx, const double* dU, int n, int ldu, double* dKinv, int ldk) {
   if (n <= 0 || ldu < n || ldk < n) return set_err(ctx, GPR_E_ARG, "bad sizes");
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, (size_t)n * n));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig, (size_t)n * n));
   double* Z = ctx->dbig;
   GPR_TRY(launch_set_identity(ctx, Z, n, n));
   GPR_TRY(trsm_ut_core(ctx, dU, n, ldu, Z, n, n, nullptr, 1));  // Z = U^{-T}
@@ -1619,13 +1574,8 @@ int gpr_potri_upper(gpr_ctx_t ctx, const double* dU, int n, int ldu, double* dKi
 
 // K^{-1} = Z^T Z (upper, round-robin K-range SYRK) mirrored to the full matrix, Z = U^{-T}
 int kinv_from_z(gpr_ctx* ctx, const double* Z, int n, double* dKinv, int ldk) {
-  GemmArgs g{};
-  g.P = Z; g.ldp = n;
-  g.Q = Z; g.ldq = n;
-  g.C = dKinv; g.ldc = ldk;
-  g.M = n; g.N = n; g.K = n;
-  g.alpha = 1.0; g.beta = 0.0;
-  g.upper = 1; g.kfrom_n = 1;
+  GemmArgs g = syrk_upper_args(Z, n, dKinv, ldk, n, n, 1.0, 0.0);
+  g.kfrom_n = 1;
   GPR_TRY(launch_gemm_tn(ctx, g, TC_SYRK));   // K^{-1} = Z^T Z (upper)
   GPR_TRY(launch_mirror_upper(ctx, dKinv, n, ldk));
   return 0;

@@ -247,6 +247,15 @@ int launch_cross_or_same(gpr_ctx* ctx, const KParams& kp, const double* dX, int 
   return launch_kernel_matrix(ctx, kp, dX, n, dXp, m, 0, out, n);
 }
 
+// full covariance of the posterior: Sigma = K(xp, xp) (eps per SE part + noise) - V^T V from
+// V = U^{-T} K(x, xp) (n x m, ld n)
+int posterior_full_cov(gpr_ctx* ctx, const KParams& kp, const double* dXp, int m, const double* V,
+                       int n, double* dvar, int ldv) {
+  GPR_TRY(launch_kernel_matrix(ctx, kp, dXp, m, nullptr, m, 1, dvar, ldv));
+  GPR_TRY(launch_gemm_tn(ctx, syrk_upper_args(V, n, dvar, ldv, m, n, -1.0, 1.0), TC_OTHER));
+  return launch_mirror_upper(ctx, dvar, m, ldv);
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,8 +268,7 @@ int gpr_fit(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d, co
   if (n <= 0 || ldk < n || nrhs <= 0 || ldy < n || !dX || !dy || !dK || !dalpha)
     return set_err(ctx, GPR_E_ARG, "bad args");
   GPR_TRY(launch_kernel_matrix_for_factor(ctx, kp, dX, n, dK, ldk));
-  HIP_TRY(ctx, hipMemcpy2DAsync(dalpha, (size_t)n * sizeof(double), dy, (size_t)ldy * sizeof(double),
-                                (size_t)n * sizeof(double), nrhs, hipMemcpyDeviceToDevice, ctx->stream));
+  GPR_TRY(copy_columns(ctx, dalpha, n, dy, ldy, nrhs));
   int hinfo = 0;
   if (ctx->fuse_y) {
     // z = U^{-T} y solved inside the factorisation (a right-hand-side column of the tile-DAG
@@ -269,7 +277,7 @@ int gpr_fit(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d, co
     GPR_TRY(potrf_core(ctx, dK, n, ldk, &hinfo, &rhs));
     if (info) *info = hinfo;
     if (hinfo != 0) return hinfo;
-    return potrs_core(ctx, dK, n, ldk, dalpha, nrhs, n, /*forward=*/!ctx->rhs_solved);
+    return potrs_core(ctx, dK, n, ldk, dalpha, nrhs, n, /*forward=*/!rhs.solved);
   }
   GPR_TRY(potrf_core(ctx, dK, n, ldk, &hinfo));
   if (info) *info = hinfo;
@@ -289,7 +297,7 @@ int gpr_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d
   if (mode == GPR_PREDICT_FULL && ldv < m) return set_err(ctx, GPR_E_ARG, "ldv < m");
   double* Kpx = dwork;
   if (!Kpx) {
-    GPR_TRY(ensure_buf(ctx, &ctx->dbig2, &ctx->big2_cap, (size_t)n * m));
+    GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)n * m));
     Kpx = ctx->dbig2;
   }
   GPR_TRY(launch_cross_or_same(ctx, kp, dX, n, dXp, m, Kpx));  // K(x, xp), n x m
@@ -304,18 +312,8 @@ int gpr_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d
     GPR_TRY(launch_fill(ctx, dvar, (size_t)m, diag_prior(kinds, nk, hp, d)));
     return trsm_ut_core(ctx, dU, n, ldu, Kpx, m, n, dvar, 0);
   }
-  // full covariance: Sigma = K(xp, xp) (eps per SE part + noise) - V^T V
   GPR_TRY(trsm_ut_core(ctx, dU, n, ldu, Kpx, m, n, nullptr, 0));
-  GPR_TRY(launch_kernel_matrix(ctx, kp, dXp, m, nullptr, m, 1, dvar, ldv));
-  GemmArgs g{};
-  g.P = Kpx; g.ldp = n;
-  g.Q = Kpx; g.ldq = n;
-  g.C = dvar; g.ldc = ldv;
-  g.M = m; g.N = m; g.K = n;
-  g.alpha = -1.0; g.beta = 1.0;
-  g.upper = 1;
-  GPR_TRY(launch_gemm_tn(ctx, g, TC_OTHER));
-  return launch_mirror_upper(ctx, dvar, m, ldv);
+  return posterior_full_cov(ctx, kp, dXp, m, Kpx, n, dvar, ldv);
 }
 
 int gpr_fit_kinv(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
@@ -327,11 +325,10 @@ int gpr_fit_kinv(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
       !dKinv)
     return set_err(ctx, GPR_E_ARG, "bad args");
   GPR_TRY(launch_kernel_matrix_for_factor(ctx, kp, dX, n, dK, ldk));
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, (size_t)n * n));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig, (size_t)n * n));
   double* Z = ctx->dbig;
   GPR_TRY(launch_set_identity(ctx, Z, n, n));
-  HIP_TRY(ctx, hipMemcpy2DAsync(dalpha, (size_t)n * sizeof(double), dy, (size_t)ldy * sizeof(double),
-                                (size_t)n * sizeof(double), nrhs, hipMemcpyDeviceToDevice, ctx->stream));
+  GPR_TRY(copy_columns(ctx, dalpha, n, dy, ldy, nrhs));
   int hinfo = 0;
   // Z = U^{-T} (identity right-hand side, lower triangular) solved in the factorisation's
   // lookahead bubbles (GPR_FUSE_KINV=0: after it, as gpr_potri_upper)
@@ -351,10 +348,10 @@ int gpr_fit_kinv(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   GPR_TRY(potrf_core(ctx, dK, n, ldk, &hinfo, fuse ? &rhs : nullptr));
   if (info) *info = hinfo;
   if (hinfo != 0) return hinfo;
-  const bool solved = fuse && ctx->rhs_solved;
+  const bool solved = rhs.solved;
   GPR_TRY(potrs_core(ctx, dK, n, ldk, dalpha, nrhs, n));
   if (!solved) GPR_TRY(trsm_ut_core(ctx, dK, n, ldk, Z, n, n, nullptr, 1));
-  if (solved && rhs.gram) return ctx->gram_full ? 0 : launch_mirror_upper(ctx, dKinv, n, ldkinv);
+  if (solved && rhs.gram) return rhs.gram_full ? 0 : launch_mirror_upper(ctx, dKinv, n, ldkinv);
   return kinv_from_z(ctx, Z, n, dKinv, ldkinv);
 }
 
@@ -381,7 +378,7 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
     // nothing to fuse for the mean alone (mu = K(xp, x) alpha); or the unfused reference order
     double* wt = dalpha;
     if (!wt) {
-      GPR_TRY(ensure_buf(ctx, &ctx->dscr_wt, &ctx->scr_wt_cap, (size_t)n * nrhs));
+      GPR_TRY(ensure_buf(ctx, ctx->dscr_wt, (size_t)n * nrhs));
       wt = ctx->dscr_wt;
     }
     int hinfo = 0;
@@ -396,20 +393,19 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
   // var = prior - ||V_j||^2; alpha = U^{-1} z by the backward sweep alone.
   double* W = dwork;
   if (!W) {
-    GPR_TRY(ensure_buf(ctx, &ctx->dbig2, &ctx->big2_cap, (size_t)n * (m + nrhs)));
+    GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)n * (m + nrhs)));
     W = ctx->dbig2;
   }
   double* Z = W + (size_t)n * m;
   GPR_TRY(launch_kernel_matrix_for_factor(ctx, kp, dX, n, dK, ldk));
   GPR_TRY(launch_cross_or_same(ctx, kp, dX, n, dXp, m, W));
-  HIP_TRY(ctx, hipMemcpy2DAsync(Z, (size_t)n * sizeof(double), dy, (size_t)ldy * sizeof(double),
-                                (size_t)n * sizeof(double), nrhs, hipMemcpyDeviceToDevice, ctx->stream));
+  GPR_TRY(copy_columns(ctx, Z, n, dy, ldy, nrhs));
   RhsSpec rhs{W, m + nrhs, n, 0, fmode == 2 ? 2 : 1, nullptr, 0};
   int hinfo = 0;
   GPR_TRY(potrf_core(ctx, dK, n, ldk, &hinfo, &rhs));
   if (info) *info = hinfo;
   if (hinfo != 0) return hinfo;
-  if (!ctx->rhs_solved) GPR_TRY(trsm_ut_core(ctx, dK, n, ldk, W, m + nrhs, n, nullptr, 0));
+  if (!rhs.solved) GPR_TRY(trsm_ut_core(ctx, dK, n, ldk, W, m + nrhs, n, nullptr, 0));
   const bool diag1 = mode == GPR_PREDICT_DIAG && nrhs == 1;  // mean and variance in one pass
   {
     TimerScope ts(ctx, TC_OTHER, 0.0);
@@ -422,9 +418,7 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
     LAUNCH_CHECK(ctx);
   }
   if (dalpha) {
-    HIP_TRY(ctx, hipMemcpy2DAsync(dalpha, (size_t)n * sizeof(double), Z, (size_t)n * sizeof(double),
-                                  (size_t)n * sizeof(double), nrhs, hipMemcpyDeviceToDevice,
-                                  ctx->stream));
+    GPR_TRY(copy_columns(ctx, dalpha, n, Z, n, nrhs));
     GPR_TRY(potrs_core(ctx, dK, n, ldk, dalpha, nrhs, n, /*forward=*/false));
   }
   if (mode == GPR_PREDICT_DIAG) {
@@ -432,16 +426,7 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
     GPR_TRY(launch_fill(ctx, dvar, (size_t)m, diag_prior(kinds, nk, hp, d)));
     return launch_colnorm_sub(ctx, W, n, n, m, dvar);
   }
-  GPR_TRY(launch_kernel_matrix(ctx, kp, dXp, m, nullptr, m, 1, dvar, ldv));
-  GemmArgs g{};
-  g.P = W; g.ldp = n;
-  g.Q = W; g.ldq = n;
-  g.C = dvar; g.ldc = ldv;
-  g.M = m; g.N = m; g.K = n;
-  g.alpha = -1.0; g.beta = 1.0;
-  g.upper = 1;
-  GPR_TRY(launch_gemm_tn(ctx, g, TC_OTHER));
-  return launch_mirror_upper(ctx, dvar, m, ldv);
+  return posterior_full_cov(ctx, kp, dXp, m, W, n, dvar, ldv);
 }
 
 int gpr_antideriv_se(gpr_ctx_t ctx, int d, const double* hp, const double* dX, int n,
@@ -460,7 +445,7 @@ int gpr_antideriv_se(gpr_ctx_t ctx, int d, const double* hp, const double* dX, i
     *k2 = i2 * hp[0] * hp[0];
   }
   if (!dk1) return 0;
-  GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, (size_t)3 * d + 2));
+  GPR_TRY(ensure_buf(ctx, ctx->dscratch, (size_t)3 * d + 2));
   std::vector<double> habl(3 * (size_t)d);  // a | b | l
   for (int i = 0; i < d; ++i) {
     habl[i] = a[i];
@@ -487,7 +472,7 @@ int gpr_integrate(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int
   const int rc = gpr_fit(ctx, kinds, nk, hp, d, dX, n, dy, ny, ldy, eps, dK, ldk, dwt, &hinfo);
   if (rc) return rc;
   // k1, k2 (update_cache!(ac, ...) :106-110)
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig2, &ctx->big2_cap, (size_t)2 * n + ny + 1));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)2 * n + ny + 1));
   double* k1 = ctx->dbig2;
   double* tt = k1 + n;
   double* dI = tt + n;
@@ -540,7 +525,7 @@ static int batch_capacity(double budget_gb, size_t per, size_t fixed, size_t cap
 // allocator may hold memory hipMemGetInfo counted as free) down to one item; then GPR_E_NOMEM.
 static int ensure_batch_buf(gpr_ctx* ctx, int* nb, const std::function<size_t(int)>& need) {
   for (;;) {
-    const int rc = ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, need(*nb));
+    const int rc = ensure_buf(ctx, ctx->dbig, need(*nb));
     if (rc != GPR_E_NOMEM || *nb <= 1) return rc;
     (void)hipGetLastError();
     ctx->err.clear();
@@ -551,12 +536,7 @@ static int ensure_batch_buf(gpr_ctx* ctx, int* nb, const std::function<size_t(in
 // The batched paths size ctx->dbig to their batch; past a call it is released again when
 // large, so a context does not keep gigabytes of scratch between calls.
 static void release_big_scratch(gpr_ctx* ctx) {
-  if (ctx->dbig && ctx->big_cap * sizeof(double) > (size_t)(1ull << 30)) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->dbig);
-    ctx->dbig = nullptr;
-    ctx->big_cap = 0;
-  }
+  if (ctx->dbig.cap * sizeof(double) > (size_t)(1ull << 30)) (void)release_buf(ctx, ctx->dbig);
 }
 
 // Cap the number of child contexts so their workspaces (bytes_each, allocated in each child's
@@ -585,18 +565,9 @@ static int run_children(gpr_ctx* ctx, int nsub, const std::function<int(gpr_ctx*
     gpr_ctx* c = ctx->cv_sub[t];
     if (c && c->dbig) {
       hipStreamSynchronize(c->stream);
-      hipFree(c->dbig);
-      c->dbig = nullptr;
-      c->big_cap = 0;
-      if (c->dbig2) hipFree(c->dbig2);  // fused fit+predict workspace of the folds
-      c->dbig2 = nullptr;
-      if (c->dpadA) hipFree(c->dpadA);  // padded copies of odd-shaped folds
-      if (c->dpadB) hipFree(c->dpadB);
-      c->dpadA = c->dpadB = nullptr;
-      c->padA_cap = c->padB_cap = 0;
-      c->big2_cap = 0;
-      c->fac_valid = false;  // cached factor data were keyed on pointers into dbig
-      c->sqinv_nb2 = 0;
+      // (with the factor caches keyed on pointers into them; dbig2: the fused fit+predict
+      // workspace of the folds, dpadA / dpadB: padded copies of odd-shaped folds)
+      for (DevBuf* b : {&c->dbig, &c->dbig2, &c->dpadA, &c->dpadB}) (void)release_buf(c, *b, true);
     }
   }
   for (int t = 0; t < nsub; ++t)
@@ -618,7 +589,7 @@ static int cv_folds(gpr_ctx* c, const int* kinds, int nk, const double* hp, int 
   // (ntst^2), xtrn, xtst, ytrn, ytst, yp, losses, then the int indices
   const size_t szK = (size_t)ntrn * ntrn, szS = (size_t)ntst * ntst;
   const size_t szv = (size_t)d * (ntrn + ntst) + ntrn + 2 * (size_t)ntst + nmine;
-  GPR_TRY(ensure_buf(c, &c->dbig, &c->big_cap, szK + szS + szv + (nidx + 1) / 2));
+  GPR_TRY(ensure_buf(c, c->dbig, szK + szS + szv + (nidx + 1) / 2));
   double* K = c->dbig;
   double* S = K + szK;
   double* xtr = S + szS;
@@ -709,7 +680,7 @@ static int cv_folds_batched(gpr_ctx* ctx, const KParams& kp, int d, const double
     return per * k + scratch + ((size_t)k * (ntrn + ntst) + 1) / 2 + 16;
   };
   int nfc = batch_capacity(ctx->cv_batch_gb, per + (ntrn + ntst + 1) / 2, scratch + 16,
-                           ctx->big_cap, nfold);
+                           ctx->dbig.cap, nfold);
   GPR_TRY(ensure_batch_buf(ctx, &nfc, need));
   const size_t nidx = (size_t)nfc * (ntrn + ntst);
   double* Kb = ctx->dbig;                 // nfc x szK
@@ -868,7 +839,7 @@ static int integ_noise_cols(gpr_ctx* c, const double* K, int ldk, int n, const d
                             int ldy, const double* k1, double k2, const double* noise, int ny,
                             int j0, int jstep, double* Iout, double* var) {
   const int nmine = (ny - j0 + jstep - 1) / jstep;
-  GPR_TRY(ensure_buf(c, &c->dbig, &c->big_cap, (size_t)n * n + 2 * (size_t)n + 2 * nmine));
+  GPR_TRY(ensure_buf(c, c->dbig, (size_t)n * n + 2 * (size_t)n + 2 * nmine));
   double* Kj = c->dbig;
   double* w = Kj + (size_t)n * n;
   double* t = w + n;
@@ -964,7 +935,7 @@ static int integ_noise_batched(gpr_ctx* ctx, const double* K, int n, const doubl
   *declined = false;
   const int n2 = (n + 15) / 16 * 16;
   const size_t per = (size_t)n2 * n2 + 2 * (size_t)n2;
-  int nbc = batch_capacity(ctx->quad_batch_gb, per + 3, 16, ctx->big_cap, ny);
+  int nbc = batch_capacity(ctx->quad_batch_gb, per + 3, 16, ctx->dbig.cap, ny);
   GPR_TRY(ensure_batch_buf(ctx, &nbc, [&](int k) { return per * k + (size_t)3 * k + 16; }));
   double* W = ctx->dbig;
   double* Bm = W + (size_t)n2 * n2 * nbc;
@@ -1086,8 +1057,7 @@ static int integ_noise_eigen(gpr_ctx* ctx, double* K, const double* k1, double k
     // Iout_j = C[:, j]' (T + s_j I)^{-1} C[:, ny] = k1' (K + s_j I)^{-1} y_j -- the reference's
     // sum_i (P'y_j)_i (P'k1)_i / (lambda_i + s_j) without the eigenvectors (any shift)
     const size_t nc = (size_t)n * (ny + 1);
-    GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap,
-                       nc + 2 * (size_t)n + 3 * (size_t)ny +
+    GPR_TRY(ensure_buf(ctx, ctx->dbig, nc + 2 * (size_t)n + 3 * (size_t)ny +
                            4 * (size_t)n * quad_tridiag_chunk(n, ny)));
     double* C = ctx->dbig;
     double* dd = C + nc;
@@ -1124,7 +1094,7 @@ static int integ_noise_eigen(gpr_ctx* ctx, double* K, const double* k1, double k
     // Jacobi (method 4, or n beyond both), lambda and T = P^T [Y | k1] directly, P never formed;
     // then the reference's diagonal update per column
     const size_t nb = (size_t)n * (ny + 1);
-    GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, nb + (size_t)n + 3 * (size_t)ny));
+    GPR_TRY(ensure_buf(ctx, ctx->dbig, nb + (size_t)n + 3 * (size_t)ny));
     double* T = ctx->dbig;
     double* lam = T + nb;
     double* dnoise = lam + n;
@@ -1171,7 +1141,7 @@ static int integ_noise_eigen(gpr_ctx* ctx, double* K, const double* k1, double k
     return set_err(ctx, GPR_E_HIP, "rocblas_set_stream failed");
   // workspace (dbig): B = [Y | k1] (n x (ny+1)), T (n x (ny+1)), lambda, E, noise, out, info
   const size_t nb = (size_t)n * (ny + 1);
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, 2 * nb + 2 * (size_t)n + 3 * (size_t)ny + 1));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig, 2 * nb + 2 * (size_t)n + 3 * (size_t)ny + 1));
   double* B = ctx->dbig;
   double* T = B + nb;
   double* lam = T + nb;
@@ -1230,7 +1200,7 @@ int gpr_integrate_noise(gpr_ctx_t ctx, const int* kinds, int nk, const double* h
     return set_err(ctx, GPR_E_ARG, "bad args");
   // kernel!(wc.kxx, ...) once (src/integrate.jl:72), k1 / k2 once (:106-110)
   // (in dbig2: the per-column worker factors K + noise_j I in its context's dbig)
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig2, &ctx->big2_cap, (size_t)n * n + n));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)n * n + n));
   double* K = ctx->dbig2;
   double* k1 = K + (size_t)n * n;
   GPR_TRY(launch_kernel_matrix(ctx, kp, dX, n, nullptr, n, 1, K, n));
@@ -1309,7 +1279,7 @@ int gpr_split_factors(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
   GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, 0.0, &kp, nullptr));
   if (part < 0 || part >= kp.nse) return set_err(ctx, GPR_E_ARG, "part out of range");
   const size_t need = (size_t)kp.nse * d * (ns + ne + nq);
-  GPR_TRY(ensure_buf(ctx, &ctx->dxs, &ctx->xs_cap, need));
+  GPR_TRY(ensure_buf(ctx, ctx->dxs, need));
   double* xs = ctx->dxs;
   double* xes = xs + (size_t)kp.nse * d * ns;
   double* xqs = xes + (size_t)kp.nse * d * ne;
@@ -1342,12 +1312,11 @@ static int split_prepare(gpr_ctx* ctx, const KParams& kp, int d, const double* d
                          SplitFactors* f) {
   const int nse = kp.nse;
   const size_t szC = (size_t)ns * nq;
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig2, &ctx->big2_cap,
-                     (size_t)nse * (szC + (size_t)Emax * nq + (size_t)ns * Emax)));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)nse * (szC + (size_t)Emax * nq + (size_t)ns * Emax)));
   f->C = ctx->dbig2;
   f->A = f->C + nse * szC;
   f->BT = f->A + (size_t)nse * Emax * nq;
-  GPR_TRY(ensure_buf(ctx, &ctx->dxs, &ctx->xs_cap, (size_t)nse * d * (ns + ne + nq)));
+  GPR_TRY(ensure_buf(ctx, ctx->dxs, (size_t)nse * d * (ns + ne + nq)));
   f->xs = ctx->dxs;
   f->xes = f->xs + (size_t)nse * d * ns;
   f->xqs = f->xes + (size_t)nse * d * ne;
@@ -1450,7 +1419,7 @@ int split_predict_pieces(gpr_ctx* ctx, const int* kinds, int nk, const double* h
       // U^{-T} solve of 32768 columns instead of four of 8192)
       int Eb = (int)std::max<size_t>(1, ((size_t)1 << 30) / per_row);
       Eb = std::min(Eb, v1 - v0);
-      GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, per_row * Eb));
+      GPR_TRY(ensure_buf(ctx, ctx->dbig, per_row * Eb));
       for (int e = v0; e < v1; e += Eb) {
         const int nr = std::min(Eb, v1 - e);
         GPR_TRY(split_kxq(ctx, nse, f.A, f.BT, f.C, ns, nq, E, e - e_lo, nr, ctx->dbig));

@@ -377,7 +377,7 @@ int pgrad_pass(gpr_ctx* ctx, const KParams& kp, const double* X, const double* c
   const int ngroup = (int)gp0.size();
   const size_t len = (size_t)m * d;
   const size_t per_group = (size_t)nslab * 4 * len;
-  GPR_TRY(ensure_buf(ctx, &ctx->dscratch, &ctx->scratch_cap, per_group * ngroup + 64));
+  GPR_TRY(ensure_buf(ctx, ctx->dscratch, per_group * ngroup + 64));
   double* partial = ctx->dscratch;
   TimerScope ts(ctx, timing_class, 0.0);
   for (int g = 0; g < ngroup; ++g) {
@@ -414,7 +414,7 @@ int pgrad_solve(gpr_ctx* ctx, const double* dU, int n, int ldu, double* B, int m
   const bool products = ctx->pgrad_solve >= 0 ? ctx->pgrad_solve != 0 : m > std::max(16, n / 512);
   *Q = B;
   if (!products) return potrs_core(ctx, dU, n, ldu, B, m, n);
-  GPR_TRY(ensure_buf(ctx, &ctx->dbig, &ctx->big_cap, (size_t)n * n + (size_t)n * m));
+  GPR_TRY(ensure_buf(ctx, ctx->dbig, (size_t)n * n + (size_t)n * m));
   double* Z = ctx->dbig;
   double* out = Z + (size_t)n * n;
   GPR_TRY(launch_set_identity(ctx, Z, n, n));
@@ -456,7 +456,7 @@ int gpr_predict_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, 
   if (want_var) {
     double* B = dwork;
     if (!B) {
-      GPR_TRY(ensure_buf(ctx, &ctx->dbig2, &ctx->big2_cap, (size_t)n * m));
+      GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)n * m));
       B = ctx->dbig2;
     }
     GPR_TRY(launch_kernel_matrix(ctx, kp, dX, n, dXp, m, 0, B, n));
@@ -464,8 +464,8 @@ int gpr_predict_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, 
   }
   const double *cs = nullptr, *csp = nullptr;
   if (kp.nper) {
-    GPR_TRY(launch_embed_unit_to(ctx, kp, dX, n, &ctx->dxs, &ctx->xs_cap));
-    GPR_TRY(launch_embed_unit_to(ctx, kp, dXp, m, &ctx->dxps, &ctx->xps_cap));
+    GPR_TRY(launch_embed_unit_to(ctx, kp, dX, n, ctx->dxs));
+    GPR_TRY(launch_embed_unit_to(ctx, kp, dXp, m, ctx->dxps));
     cs = ctx->dxs;
     csp = ctx->dxps;
   }

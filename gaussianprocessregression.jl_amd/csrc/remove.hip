@@ -343,16 +343,15 @@ int gpr_fit_remove(gpr_ctx_t ctx, const double* dK, int n0, int ldk, const int* 
   }
   std::copy(idx, idx + r, hk.begin() + np);
   const size_t wdoubles = (size_t)RM_R * np;
-  GPR_TRY(ensure_buf(ctx, &ctx->drmw, &ctx->rmw_cap, wdoubles + (hk.size() + 1) / 2));
-  GPR_TRY(ensure_buf(ctx, &ctx->dahand, &ctx->ahand_cap, (size_t)nblk * RM_ROT));
+  GPR_TRY(ensure_buf(ctx, ctx->drmw, wdoubles + (hk.size() + 1) / 2));
+  GPR_TRY(ensure_buf(ctx, ctx->dahand, (size_t)nblk * RM_ROT));
   double* wbuf = ctx->drmw;
   int* dkeep = reinterpret_cast<int*>(ctx->drmw + wdoubles);
   const int* didx = dkeep + np;
   HIP_TRY(ctx, hipMemcpyAsync(dkeep, hk.data(), hk.size() * sizeof(int), hipMemcpyHostToDevice, st));
 
   // dKout receives a new factor: whatever the context cached for that buffer is stale
-  ctx->fac_valid = false;
-  ctx->sqinv_nb2 = 0;
+  ctx->fc.factor_forget();
 
   const int rowlim = std::min(nblk, idx[0] / RM_NB) * RM_NB;
   {
@@ -367,7 +366,7 @@ int gpr_fit_remove(gpr_ctx_t ctx, const double* dK, int n0, int ldk, const int* 
   // 16.1, r = 1 middle 9.5 vs 7.9, r = 8 34.2 vs 27.4, r = 16 60.3 vs 47.1, r = 128 427 vs 316 -- a hop
   // of the sweep carries the store of the tile above the diagonal and the drain before the publish
   const bool sweep = ctx->remove_sweep > 0;
-  int* sync = ctx->dinfo + 8;  // dinfo[8..9]: ticket / blocks done
+  int* sync = ctx->dinfo + INFO_SKINNY;
   {
     TimerScope ts(ctx, TC_REMOVE_UPDATE, 0.0);
     for (int s0 = 0; s0 < r; s0 += RM_R) {
@@ -384,7 +383,7 @@ int gpr_fit_remove(gpr_ctx_t ctx, const double* dK, int n0, int ldk, const int* 
       g.rs = rs;
       for (int s = 0; s < rs; ++s) g.q[s] = idx[s0 + s] - (s0 + s);
       if (sweep) {
-        HIP_TRY(ctx, hipMemsetAsync(sync, 0, 2 * sizeof(int), st));
+        HIP_TRY(ctx, hipMemsetAsync(sync, 0, INFO_SKINNY_N * sizeof(int), st));
         remove_sweep_kernel<<<nblk - a0, RM_THREADS, RM_LDS, st>>>(
             A, ld, keep, dKout, (size_t)ldo, np, a0, g, wbuf, ctx->dahand, sync);
         LAUNCH_CHECK(ctx);
@@ -402,9 +401,7 @@ int gpr_fit_remove(gpr_ctx_t ctx, const double* dK, int n0, int ldk, const int* 
     }
   }
   // alpha' = K'^{-1} y by the two sweeps on the new factor (which establish the factor cache)
-  HIP_TRY(ctx, hipMemcpy2DAsync(dalpha, (size_t)np * sizeof(double), dy,
-                                (size_t)ldy * sizeof(double), (size_t)np * sizeof(double), nrhs,
-                                hipMemcpyDeviceToDevice, st));
+  GPR_TRY(copy_columns(ctx, dalpha, np, dy, ldy, nrhs));
   GPR_TRY(potrs_core(ctx, dKout, np, ldo, dalpha, nrhs, np));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return 0;

@@ -154,7 +154,7 @@ int gpr_sample_prior(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, 
   // Sigma .+ shift on every element (src/distributions.jl:21).  After an upper-only assembly
   // the tile-DAG mirrors the shifted tiles; after a full one every element is shifted here:
   // either way the strict lower triangle ends as that of the matrix that was factored.
-  GPR_TRY(launch_add_scalar(ctx, dK, n, ldk, shift, ctx->kup_ptr == dK ? 1 : 2));
+  GPR_TRY(launch_add_scalar(ctx, dK, n, ldk, shift, ctx->fc.kup_pending(dK) ? 1 : 2));
   int hinfo = 0;
   GPR_TRY(potrf_core(ctx, dK, n, ldk, &hinfo));
   if (info) *info = hinfo;

@@ -1349,12 +1349,7 @@ namespace {
 // the work copy and the exchange buffers (4 n^2 doubles) are not kept past the call once they
 // pass 1 GB (n > ~5.8k; re-allocating costs far less than the reduction itself)
 int release_eig_scratch(gpr_ctx* ctx) {
-  if (ctx->deig && ctx->eig_cap * sizeof(double) > (size_t)(1ull << 30)) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(ctx->deig));
-    ctx->deig = nullptr;
-    ctx->eig_cap = 0;
-  }
+  if (ctx->deig.cap * sizeof(double) > (size_t)(1ull << 30)) return release_buf(ctx, ctx->deig);
   return 0;
 }
 
@@ -1443,7 +1438,7 @@ int sym_tridiag(gpr_ctx* ctx, const double* dA, int n, int lda, double* dB, int 
   const size_t nG = df ? nW : gv ? 8 * ld : 0;
   const size_t nA = df ? (size_t)n * 2 * DF_NB * P : 0;  // (DF: the panel's dot partials)
   const size_t need = 4 * nW + (size_t)n * P + nA + (size_t)n + 8 + nI + nQ + nG;
-  GPR_TRY(ensure_buf(ctx, &ctx->deig, &ctx->eig_cap, need));
+  GPR_TRY(ensure_buf(ctx, ctx->deig, need));
   double* W = ctx->deig;
   double* V = W + nW;
   double* cpub = V + nW;
