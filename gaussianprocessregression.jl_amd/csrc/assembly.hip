@@ -615,7 +615,9 @@ void launch_cross(gpr_ctx* ctx, const KParams& kp, const double* xs, int n, cons
 // started from C = -|y_a|^2 - |y_b|^2 (one VALU add per element), so the FP64 VALU is left with
 // exp (kexp_s2) and the part sum.  Rounding: |error of D| <~ (d + 1) u (|y_a|^2 + |y_b|^2),
 // ~1e-15 absolute at the default hp (K within rtol 1e-13 of the reference's difference form,
-// tests/test_gpu_parity.py); a same-object diagonal gets D = 0 exactly and diagonal tiles are
+// tests/test_gpu_parity.py; the worst case, (3 d + 4) u (|y_a|^2 + |y_b|^2) on top of the
+// difference form's own, is what tests/test_gpu_kernel_domain.py holds the kernels to far from
+// the unit cube: DESIGN 3.5.1); a same-object diagonal gets D = 0 exactly and diagonal tiles are
 // made bitwise symmetric.  GPR_KBUILD_EXACT=1 selects the reference's difference form
 // (x .* l - x' .* l)^2 in kmat_sym2/cross2.
 // Measured (tools/kbuild_bench, SE+SE+WN N = 32768 d = 8, same box): difference form 2.43 ms,

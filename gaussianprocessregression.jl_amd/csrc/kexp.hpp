@@ -14,8 +14,8 @@
 // Tang's reduction with x = -dist (already in range): kf = x 256/ln2 + 1.5 2^52 holds
 // n = rint(x 256/ln2) in its low word (magic-constant rounding: no rndne / cvt), r = x -
 // n ln2/256 in two Cody-Waite steps, a degree-4 expm1 (truncation < 0.2 ulp), exp(x) =
-// 2^(n >> 8) T[n & 255] (1 + expm1(r)) with sigma^2 folded into the table (one rounding of
-// s2 * T[j]).
+// 2^(n >> 8) T[n & 255] (1 + expm1(r)) with sigma^2 folded into the table (fl(fl(sigma sigma)
+// T[j]): two roundings on top of T[j]'s own).  Error budget and its test: DESIGN 3.5.1.
 static __device__ __forceinline__ double kexp_core(double x, const double* ts) {
   const double kf = fma(x, 369.3299304675746, 6755399441055744.0);
   const double nf = kf - 6755399441055744.0;
