@@ -219,7 +219,7 @@ enum {
 enum TimingClass {
   TC_KBUILD = 0, TC_SYRK = 1, TC_PANEL = 2, TC_TRSM_GEMM = 3, TC_OTHER = 4, TC_GEMM_PIPE = 5,
   TC_DAG = 6, TC_DAG_SOLVE = 7, TC_PGRAD_MEAN = 8, TC_PGRAD_VAR = 9, TC_PGRAD_SOLVE = 10,
-  TC_APPEND_SOLVE = 11, TC_REMOVE_UPDATE = 12, TC_N = 13
+  TC_APPEND_SOLVE = 11, TC_REMOVE_UPDATE = 12, TC_CV_GRAM = 13, TC_CV_SOLVE = 14, TC_N = 15
 };
 
 struct TimedLaunch {
@@ -357,6 +357,9 @@ struct gpr_ctx {
                                 // MFMA D layout instead of 1-KB column segments
   int cv_batch = 1;             // GPR_CV_BATCH=0: cv_batch folds one by one on child contexts
   double cv_batch_gb = 16.0;    // GPR_CV_BATCH_GB: device-memory budget of a batched launch
+  int cv_kfold_gram = -1;       // GPR_CV_KFOLD_GRAM: gpr_cv_kfold's P_FF as fold Grams of Z = U^{-T}
+                                // (1), or gathered from the full K^{-1} (0); -1 auto: the Grams for
+                                // folds of up to 128 points, the gather above (cvfold.hip)
   double quad_batch_gb = 16.0;  // GPR_QUAD_BATCH_GB: the same for the quadrature's columns
   int quad_eigen = -1;          // GPR_QUAD_EIGEN: sample_noise quadrature path (-1 auto)
   int quad_seq = 0;             // GPR_QUAD_SEQ=1: its per-column factorisations one at a time

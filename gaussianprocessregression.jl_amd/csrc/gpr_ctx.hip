@@ -300,6 +300,7 @@ const Knob kKnobs[] = {
     {"GPR_CV_STREAMS", &gpr_ctx::cv_streams, nullptr},
     {"GPR_CV_BATCH", &gpr_ctx::cv_batch, nullptr},
     {"GPR_CV_BATCH_GB", nullptr, &gpr_ctx::cv_batch_gb},
+    {"GPR_CV_KFOLD_GRAM", &gpr_ctx::cv_kfold_gram, nullptr},
     {"GPR_QUAD_BATCH_GB", nullptr, &gpr_ctx::quad_batch_gb},
     {"GPR_QUAD_EIGEN", &gpr_ctx::quad_eigen, nullptr},
     {"GPR_QUAD_SEQ", &gpr_ctx::quad_seq, nullptr},

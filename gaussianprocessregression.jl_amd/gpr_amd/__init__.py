@@ -58,7 +58,19 @@ from .core import (
     similar,
 )
 
-from .crossval import ChiSq, Mahalanobis, MSE, cv_batch, cv_step, cv_step_, kfoldcv
+from .crossval import (
+    ChiSq,
+    Mahalanobis,
+    MSE,
+    complement_folds,
+    cv_batch,
+    cv_kfold,
+    cv_loo,
+    cv_step,
+    cv_step_,
+    is_kfold_complement,
+    kfoldcv,
+)
 from .distributions import GaussianProcess, NormalDistribution, sample, sample_posterior
 from .integrate import antideriv, antideriv2, erf_integ, gauss_integ, integrate
 from .train import (

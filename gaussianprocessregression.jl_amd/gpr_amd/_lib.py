@@ -92,6 +92,7 @@ _SIGS = {
     "gpr_integrate_noise": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _dp, _dp, _dp, _d, _dp,
                                  _dp]),
     "gpr_cv_batch": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _ip, _i, _ip, _i, _i, _i, _d, _dp]),
+    "gpr_cv_kfold": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _ip, _i, _i, _i, _d, _dp, _dp, _dp]),
     "gpr_syev_apply": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _ip]),
     "gpr_sytrd_apply": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _p]),
     "gpr_split_predict_rows": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _ip,

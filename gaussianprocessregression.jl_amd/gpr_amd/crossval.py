@@ -90,7 +90,9 @@ def _cv(md: C.GPRModel, cost, dx, dy, n: int, trn: np.ndarray, tst: np.ndarray,
 def cv_batch(md: C.GPRModel, cost, x, y, cvset, eps: float = C.EPS_DEFAULT) -> np.ndarray:
     """cv_batch(md, cost, x, y, (trn, tst)) (src/crossval.jl:13-35): for every fold, a model
     with md's kernel and hyperparameters fitted on x[:, trn[i]], y[trn[i]] predicts
-    x[:, tst[i]] with the full covariance; returns the fold losses."""
+    x[:, tst[i]] with the full covariance; returns the fold losses.  When every trn[i] is the
+    complement of tst[i] (``is_kfold_complement``), ``cv_kfold`` gives the same losses from one
+    factorisation of all points."""
     x = np.asarray(x, dtype=np.float64)
     x = x[None, :] if x.ndim == 1 else x
     y = np.asarray(y, dtype=np.float64)
@@ -101,6 +103,94 @@ def cv_batch(md: C.GPRModel, cost, x, y, cvset, eps: float = C.EPS_DEFAULT) -> n
     trn, tst = cvset
     return _cv(md, cost, md.ctx.colmajor(x), md.ctx.colmajor(y), y.shape[0],
                _fold_matrix(trn, "trn"), _fold_matrix(tst, "tst"), eps)
+
+
+def complement_folds(n: int, tst: Sequence):
+    """The training sets that make ``(trn, tst)`` a ``cv_batch`` cvset of complementary folds:
+    trn[i] = every index of 0..n-1 that tst[i] does not hold, ascending.  Host only."""
+    trn = []
+    for f in tst:
+        keep = np.ones(n, dtype=bool)
+        keep[np.asarray(f, dtype=np.int64)] = False
+        trn.append(np.flatnonzero(keep))
+    return trn
+
+
+def is_kfold_complement(n: int, cvset) -> bool:
+    """True when every trn[i] of cvset = (trn, tst) is exactly the complement of tst[i] in
+    0..n-1 (no index twice, none missing): the folds ``cv_kfold`` computes.  Host only."""
+    trn, tst = cvset
+    if len(trn) != len(tst):
+        return False
+    for a, b in zip(trn, tst):
+        a = np.asarray(a, dtype=np.int64).ravel()
+        b = np.asarray(b, dtype=np.int64).ravel()
+        both = np.concatenate([a, b])
+        if both.size != n or both.min(initial=0) < 0 or both.max(initial=0) >= n:
+            return False
+        if np.unique(both).size != n:
+            return False
+    return True
+
+
+def _xy(md: C.GPRModel, x, y):
+    x = np.asarray(x, dtype=np.float64)
+    x = x[None, :] if x.ndim == 1 else x
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or x.shape[1] != y.shape[0]:
+        raise ValueError("x and y size mismatch.")
+    if x.shape[0] != md.d:
+        raise ValueError("x dimension does not match the model")
+    return x, y
+
+
+def _cv_kfold(md: C.GPRModel, code: int, x, y, tst: np.ndarray, eps: float, pred: bool):
+    ctx = md.ctx
+    kinds, nk = C._kinds_arr(md.covar)
+    hpa, hpp = C._hp_arr(md.params)
+    nfold, ntst = tst.shape
+    n = y.shape[0]
+    dx, dy = ctx.colmajor(x), ctx.colmajor(y)
+    lss = np.zeros(nfold)
+    mu = np.zeros((nfold, ntst)) if pred else None
+    var = np.zeros((nfold, ntst)) if pred else None
+    dp = ctypes.POINTER(ctypes.c_double)
+    rc = lib.gpr_cv_kfold(ctx.h, kinds, nk, hpp, md.d, C._ptr(dx), n, C._ptr(dy),
+                          tst.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ntst, nfold, code, eps,
+                          lss.ctypes.data_as(dp), mu.ctypes.data_as(dp) if pred else None,
+                          var.ctypes.data_as(dp) if pred else None)
+    if rc > 0:
+        raise C.PosDefException(rc)
+    ctx.check(rc, "gpr_cv_kfold")
+    return lss, mu, var
+
+
+def cv_kfold(md: C.GPRModel, cost, x, y, tst, eps: float = C.EPS_DEFAULT,
+             return_pred: bool = False):
+    """The losses of ``cv_batch(md, cost, x, y, (complement_folds(n, tst), tst))`` from ONE
+    factorisation of all n points (``gpr_cv_kfold``): every fold tests tst[i] and trains on all
+    the other points.  With K the kernel matrix of all points (eps and noise on its diagonal),
+    P = K^-1 and alpha = K^-1 y, the fold's posterior covariance is (P_FF)^-1 and its residual
+    (P_FF)^-1 alpha_F -- exact, and about cond(K) * 1e-16 in rounding.
+
+    tst: a list of equal-length index arrays (0-based), e.g. the second element of ``kfoldcv``;
+    folds may overlap and need not cover the points.  Returns the fold losses, or with
+    ``return_pred`` (lss, mu, var): per fold the posterior mean at its test points and the
+    diagonal of its posterior covariance."""
+    code = _cost_code(cost)
+    x, y = _xy(md, x, y)
+    lss, mu, var = _cv_kfold(md, code, x, y, _fold_matrix(tst, "tst"), eps, return_pred)
+    return (lss, mu, var) if return_pred else lss
+
+
+def cv_loo(md: C.GPRModel, x, y, eps: float = C.EPS_DEFAULT):
+    """Leave-one-out predictions of all n points from one factorisation: (mu, var) with
+    mu[i] = y[i] - alpha[i] / P[i, i] and var[i] = 1 / P[i, i] (P = K^-1, alpha = K^-1 y) --
+    ``cv_kfold`` with the n one-point folds [0], [1], ..."""
+    x, y = _xy(md, x, y)
+    tst = np.arange(y.shape[0], dtype=np.int32).reshape(-1, 1)
+    _, mu, var = _cv_kfold(md, GPR_COST_MSE, x, y, np.ascontiguousarray(tst), eps, True)
+    return mu[:, 0].copy(), var[:, 0].copy()
 
 
 def cv_step(md: C.GPRModel, cost, xtr, ytr, xtst, ytst, eps: float = C.EPS_DEFAULT) -> float:
