@@ -219,7 +219,8 @@ enum {
 enum TimingClass {
   TC_KBUILD = 0, TC_SYRK = 1, TC_PANEL = 2, TC_TRSM_GEMM = 3, TC_OTHER = 4, TC_GEMM_PIPE = 5,
   TC_DAG = 6, TC_DAG_SOLVE = 7, TC_PGRAD_MEAN = 8, TC_PGRAD_VAR = 9, TC_PGRAD_SOLVE = 10,
-  TC_APPEND_SOLVE = 11, TC_REMOVE_UPDATE = 12, TC_CV_GRAM = 13, TC_CV_SOLVE = 14, TC_N = 15
+  TC_APPEND_SOLVE = 11, TC_REMOVE_UPDATE = 12, TC_CV_GRAM = 13, TC_CV_SOLVE = 14,
+  TC_LOO_SMALL = 15, TC_LOO_SYRK = 16, TC_N = 17
 };
 
 struct TimedLaunch {
@@ -553,6 +554,17 @@ int diag_inverse_blocks(gpr_ctx* ctx, const double* dU, int ldu, int n, int b0);
 int trsm_ut_core(gpr_ctx* ctx, const double* dU, int n, int ldu, double* dB, int nrhs,
                  int ldb, double* norm_out, int lower_rhs);
 int kinv_from_z(gpr_ctx* ctx, const double* Z, int n, double* dKinv, int ldk);
+// cvfold.hip: K = U^T U into dK (ldk), Z = U^{-T} (ld n), alpha = K^{-1} y and, where P is not
+// null, P = K^{-1} in full (ld n), in gpr_fit_kinv's order of calls; *hinfo > 0: not positive definite
+int fit_z_alpha(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, const double* dy,
+                double* K, int ldk, double* Z, double* dalpha, double* P, int* hinfo);
+// mll.hip: the host part of gpr_mll_grad -- grad[D] (host) = -0.5 sum_ab (a_a a_b - M_ab) dK_i,ab
+// from one fused pass over the upper 64 x 64 tiles of M (n x n, ldm; a diagonal tile is read in
+// full), in hp order, G .*= hp with log_scale.  gpr_mll_grad: M = K^{-1}, a = alpha; gpr_loo_grad:
+// a = 0 and its weight matrix.  Synchronises.
+int weighted_dk_sums(gpr_ctx* ctx, const KParams& kp, int D, const int* kinds, int nk,
+                     const double* hp, int d, const double* dX, int n, const double* dM, int ldm,
+                     const double* da, int log_scale, double* grad);
 // symmetric eigendecomposition A = P diag(lam) P^T applied to B: lam (n, device) and
 // B <- P^T B (n x m, ld ldb), A read only; *sweeps may be null.  method 0: tridiagonal
 // reduction + divide and conquer (tridiag.hip, dstedc.hip) where n fits them, else block

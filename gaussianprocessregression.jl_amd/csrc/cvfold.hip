@@ -307,6 +307,37 @@ int cf_slabs(int n, int nfold) {
 
 }  // namespace
 
+// K = U^T U into dK (n x n, ldk: upper U, strict lower K, as gpr_fit), Z = U^{-T} (n x n, ld n,
+// lower triangular: what lies above its diagonal is not to be relied on), alpha = K^{-1} y, and,
+// where P is given, P = K^{-1} in full (n x n, ld n) -- gpr_fit_kinv's order of calls.  The front
+// half of gpr_cv_kfold and the whole of gpr_fit_loo.  *hinfo > 0: K is not positive definite.
+int fit_z_alpha(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, const double* dy,
+                double* K, int ldk, double* Z, double* dalpha, double* P, int* hinfo) {
+  GPR_TRY(launch_kernel_matrix_for_factor(ctx, kp, dX, n, K, ldk));
+  GPR_TRY(launch_set_identity(ctx, Z, n, n));
+  GPR_TRY(copy_columns(ctx, dalpha, n, dy, n, 1));
+  RhsSpec rhs{Z, n, n, 1, ctx->fused_rhs == 2 ? 2 : 1, nullptr, 0};
+  const int fuse = ctx->fuse_kinv >= 0 ? ctx->fuse_kinv : 2;
+  if (P && fuse == 2) {
+    rhs.gram = P;
+    rhs.ldg = n;
+  }
+  *hinfo = 0;
+  GPR_TRY(potrf_core(ctx, K, n, ldk, hinfo, &rhs));
+  if (*hinfo != 0) return 0;
+  const bool solved = rhs.solved;
+  GPR_TRY(potrs_core(ctx, K, n, ldk, dalpha, 1, n));
+  if (!solved) GPR_TRY(trsm_ut_core(ctx, K, n, ldk, Z, n, n, nullptr, 1));
+  if (P) {
+    if (solved && rhs.gram) {
+      if (!rhs.gram_full) GPR_TRY(launch_mirror_upper(ctx, P, n, n));
+    } else {
+      GPR_TRY(kinv_from_z(ctx, Z, n, P, n));
+    }
+  }
+  return 0;
+}
+
 extern "C" int gpr_cv_kfold(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                             const double* dX, int n, const double* dy, const int* tst, int ntst,
                             int nfold, int cost, double eps, double* lss, double* mu,
@@ -385,28 +416,9 @@ extern "C" int gpr_cv_kfold(gpr_ctx_t ctx, const int* kinds, int nk, const doubl
   int* dfinfo = dfirst + nfold;
 
   // ---- one factorisation: K = U^T U, Z = U^{-T}, alpha = K^{-1} y (gpr_fit_kinv's order) -----
-  GPR_TRY(launch_kernel_matrix_for_factor(ctx, kp, dX, n, K, n));
-  GPR_TRY(launch_set_identity(ctx, Z, n, n));
-  GPR_TRY(copy_columns(ctx, dalpha, n, dy, n, 1));
-  RhsSpec rhs{Z, n, n, 1, ctx->fused_rhs == 2 ? 2 : 1, nullptr, 0};
-  const int fuse = ctx->fuse_kinv >= 0 ? ctx->fuse_kinv : 2;
-  if (!gram_route && fuse == 2) {
-    rhs.gram = P;
-    rhs.ldg = n;
-  }
   int hinfo = 0;
-  GPR_TRY(potrf_core(ctx, K, n, n, &hinfo, &rhs));
+  GPR_TRY(fit_z_alpha(ctx, kp, dX, n, dy, K, n, Z, dalpha, P, &hinfo));
   if (hinfo != 0) return hinfo;
-  const bool solved = rhs.solved;
-  GPR_TRY(potrs_core(ctx, K, n, n, dalpha, 1, n));
-  if (!solved) GPR_TRY(trsm_ut_core(ctx, K, n, n, Z, n, n, nullptr, 1));
-  if (!gram_route) {
-    if (solved && rhs.gram) {
-      if (!rhs.gram_full) GPR_TRY(launch_mirror_upper(ctx, P, n, n));
-    } else {
-      GPR_TRY(kinv_from_z(ctx, Z, n, P, n));
-    }
-  }
 
   HIP_TRY(ctx, hipMemcpyAsync(didx, tst, nout * sizeof(int), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(dfirst, hfirst.data(), (size_t)nfold * sizeof(int),

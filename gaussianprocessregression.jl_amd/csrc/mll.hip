@@ -538,28 +538,12 @@ void launch_grad_pass(gpr_ctx* ctx, const KParams& kp, const double* X, const do
 
 }  // namespace
 
-extern "C" {
-
-int gpr_mll(gpr_ctx_t ctx, const double* dU, int n, int ldu, const double* dy,
-            const double* dalpha, double* out) {
-  if (n <= 0 || ldu < n || !dU || !dy || !dalpha || !out) return set_err(ctx, GPR_E_ARG, "bad args");
-  GPR_TRY(ensure_buf(ctx, ctx->dscratch, 64));
-  mll_terms_kernel<<<1, 1024, 0, ctx->stream>>>(dU, (size_t)ldu, n, dy, dalpha, ctx->dscratch);
-  LAUNCH_CHECK(ctx);
-  double h[2];
-  HIP_TRY(ctx, hipMemcpyAsync(h, ctx->dscratch, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *out = 0.5 * (h[0] + 2.0 * h[1] + (double)n * std::log(2.0 * M_PI));
-  return 0;
-}
-
-int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
-                 const double* dX, int n, const double* dKinv, int ldk, const double* dalpha,
-                 double eps, int log_scale, double* grad) {
-  KParams kp;
-  int D = 0;
-  GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, &D));
-  if (n <= 0 || ldk < n || !dX || !dKinv || !dalpha || !grad) return set_err(ctx, GPR_E_ARG, "bad args");
+// The host part of the fused gradient: launch, fixed-order reduction, assembly in hp order, log
+// scale.  Shared by gpr_mll_grad (M = K^{-1}, a = alpha) and gpr_loo_grad (loo.hip: a = 0 and its
+// own weight matrix); the kernels and their template arguments are the same for both.
+int weighted_dk_sums(gpr_ctx* ctx, const KParams& kp, int D, const int* kinds, int nk,
+                     const double* hp, int d, const double* dX, int n, const double* dKinv, int ldk,
+                     const double* dalpha, int log_scale, double* grad) {
   const int nt = (n + GT - 1) / GT;
   const long long nblk = (long long)nt * (nt + 1) / 2;
   // per stationary part its hp width (d + 1; Periodic 2d + 1), then the WhiteNoise slot
@@ -606,6 +590,31 @@ int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   if (log_scale)
     for (int i = 0; i < D; ++i) grad[i] *= hp[i];
   return 0;
+}
+
+extern "C" {
+
+int gpr_mll(gpr_ctx_t ctx, const double* dU, int n, int ldu, const double* dy,
+            const double* dalpha, double* out) {
+  if (n <= 0 || ldu < n || !dU || !dy || !dalpha || !out) return set_err(ctx, GPR_E_ARG, "bad args");
+  GPR_TRY(ensure_buf(ctx, ctx->dscratch, 64));
+  mll_terms_kernel<<<1, 1024, 0, ctx->stream>>>(dU, (size_t)ldu, n, dy, dalpha, ctx->dscratch);
+  LAUNCH_CHECK(ctx);
+  double h[2];
+  HIP_TRY(ctx, hipMemcpyAsync(h, ctx->dscratch, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *out = 0.5 * (h[0] + 2.0 * h[1] + (double)n * std::log(2.0 * M_PI));
+  return 0;
+}
+
+int gpr_mll_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                 const double* dX, int n, const double* dKinv, int ldk, const double* dalpha,
+                 double eps, int log_scale, double* grad) {
+  KParams kp;
+  int D = 0;
+  GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, &D));
+  if (n <= 0 || ldk < n || !dX || !dKinv || !dalpha || !grad) return set_err(ctx, GPR_E_ARG, "bad args");
+  return weighted_dk_sums(ctx, kp, D, kinds, nk, hp, d, dX, n, dKinv, ldk, dalpha, log_scale, grad);
 }
 
 }  // extern "C"

@@ -14,7 +14,9 @@ from .core import (
     GPRModel,
     GPRPredictCache,
     GPRSplitPredictCache,
+    LeaveOneOut,
     LogScale,
+    LooLossCache,
     MarginalLikelihood,
     Matern32,
     Matern52,
@@ -60,6 +62,7 @@ from .core import (
 
 from .crossval import (
     ChiSq,
+    LogPredictive,
     Mahalanobis,
     MSE,
     complement_folds,

@@ -35,6 +35,7 @@ GPR_PREDICT_FULL = 2
 GPR_COST_MSE = 1
 GPR_COST_CHISQ = 2
 GPR_COST_MAHALANOBIS = 3
+GPR_COST_LOGPRED = 4  # leave-one-out only (gpr_loo, gpr_loo_grad)
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"libgpr_hip.so not found at {LIB_PATH}: build it with "
@@ -93,6 +94,9 @@ _SIGS = {
                                  _dp]),
     "gpr_cv_batch": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _ip, _i, _ip, _i, _i, _i, _d, _dp]),
     "gpr_cv_kfold": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _ip, _i, _i, _i, _d, _dp, _dp, _dp]),
+    "gpr_fit_loo": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _d, _p, _i, _p, _p, _ip]),
+    "gpr_loo": (_i, [_p, _i, _p, _i, _p, _i, _dp]),
+    "gpr_loo_grad": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _d, _i, _i, _dp, _dp]),
     "gpr_syev_apply": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _ip]),
     "gpr_sytrd_apply": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _p]),
     "gpr_split_predict_rows": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _ip,

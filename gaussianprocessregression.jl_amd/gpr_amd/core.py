@@ -456,6 +456,34 @@ class MarginalLikelihood:
     """Negative log marginal likelihood (src/loss_grad.jl:5,39-52)."""
 
 
+class LeaveOneOut:
+    """Leave-one-out pseudo-likelihood (Rasmussen & Williams 5.4.2): the sum over the n points of
+    ``cost`` on the prediction of point i from all the others.  cost: ``LogPredictive()`` (the
+    default: the negative log predictive density), ``MSE()``, ``ChiSq()`` or ``Mahalanobis()`` --
+    for these three the SUM of ``cv_kfold``'s losses over the n one-point folds.  A loss on the
+    reference's AbstractLoss seam (src/cost.jl), which ships only MarginalLikelihood: value and
+    gradient come from one factorisation (gpr_fit_loo / gpr_loo / gpr_loo_grad)."""
+
+    def __init__(self, cost=None):
+        if cost is None:
+            from .crossval import LogPredictive
+            cost = LogPredictive()
+        self.cost = cost
+
+    def __repr__(self):
+        return f"LeaveOneOut({type(self.cost).__name__}())"
+
+
+def _loo_crit(cost: LeaveOneOut) -> int:
+    """The C ABI's criterion code of a LeaveOneOut loss; TypeError for any other inner cost."""
+    from . import crossval as X
+    c = cost.cost
+    if not isinstance(c, (X.LogPredictive, X.MSE, X.ChiSq, X.Mahalanobis)):
+        raise TypeError(f"no leave-one-out criterion for {c!r} "
+                        "(LogPredictive, MSE, ChiSq, Mahalanobis)")
+    return c.LOO_CRIT if isinstance(c, X.LogPredictive) else c.COST
+
+
 class LogScale:
     pass
 
@@ -503,9 +531,42 @@ class MllGradCache(MllLossCache):
         self.Kinv = self.ctx.empty(md.n, md.n)
 
 
+class LooLossCache:
+    """The loss-only cache of LeaveOneOut: the factor U (kchol_base), alpha = K^{-1} y and
+    pdiag = diag(K^{-1}), filled by gpr_fit_loo from one factorisation without forming K^{-1}.
+    ``capacity`` as on the other caches.  (Not an MllLossCache: append_ / remove_ would leave
+    pdiag behind.)"""
+
+    def __init__(self, md: GPRModel, capacity: Optional[int] = None):
+        self.ctx = md.ctx
+        self.hp = md.params.copy()
+        self.ld = _cache_ld(md, capacity)
+        self.kchol_base = self.ctx.empty(self.ld, self.ld)  # column-major N x N
+        self.alpha = self.ctx.empty(md.n)
+        self.pdiag = self.ctx.empty(md.n)
+        self.info = 0
+
+
+def _update_loo_cache_(tc: LooLossCache, hp, md: GPRModel, eps: float = EPS_DEFAULT):
+    ctx = md.ctx
+    tc.hp = np.array(hp, dtype=np.float64)
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(tc.hp)
+    info = ctypes.c_int(0)
+    rc = lib.gpr_fit_loo(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(md.dsample()), eps,
+                         _ptr(tc.kchol_base), tc.ld, _ptr(tc.alpha), _ptr(tc.pdiag),
+                         ctypes.byref(info))
+    tc.info = info.value
+    if info.value != 0:
+        raise PosDefException(info.value)
+    ctx.check(rc, "gpr_fit_loo")
+
+
 def update_cache_(tc: MllLossCache, hp, md: GPRModel, eps: float = EPS_DEFAULT):
     """update_cache!(tc, hp, md) (src/cost.jl:74-111): K, in-place POTRF, alpha = K^{-1} y,
-    and for MllGradCache also K^{-1}."""
+    and for MllGradCache also K^{-1}; for LooLossCache diag(K^{-1}) instead (gpr_fit_loo)."""
+    if isinstance(tc, LooLossCache):
+        return _update_loo_cache_(tc, hp, md, eps)
     ctx = md.ctx
     tc.hp = np.array(hp, dtype=np.float64)
     kinds, nk = _kinds_arr(md.covar)
@@ -545,10 +606,76 @@ def _mll_grad(md: GPRModel, tc: MllGradCache, eps=EPS_DEFAULT, log_scale=False) 
     return g
 
 
+def _loo_cache_check(tc, grad: bool):
+    """A LeaveOneOut call's cache: an MllGradCache (K^{-1}) for the gradient, that or a
+    LooLossCache (diag K^{-1}) for the value; anything else is refused before any device work."""
+    if isinstance(tc, MllGradCache) or (not grad and isinstance(tc, LooLossCache)):
+        return tc
+    want = "an MllGradCache" if grad else "a LooLossCache or an MllGradCache"
+    raise TypeError(f"LeaveOneOut needs {want}, not {type(tc).__name__}")
+
+
+def _loo_value(md: GPRModel, tc, crit: int) -> float:
+    """The criterion from an up-to-date cache of either type: nothing refitted."""
+    ctx = md.ctx
+    out = ctypes.c_double(0.0)
+    if isinstance(tc, LooLossCache):
+        dp, incp = tc.pdiag, 1
+    else:  # the diagonal of the MllGradCache's K^{-1} (leading dimension n)
+        dp, incp = tc.Kinv, md.n + 1
+    ctx.check(lib.gpr_loo(ctx.h, crit, _ptr(dp), incp, _ptr(tc.alpha), md.n, ctypes.byref(out)),
+              "gpr_loo")
+    return out.value
+
+
+def _loo_grad(md: GPRModel, tc: MllGradCache, crit: int, eps=EPS_DEFAULT, log_scale=False,
+              want_value=False):
+    """(gradient, value or None) of the criterion from an updated MllGradCache (gpr_loo_grad:
+    tc.Kinv and tc.alpha are read only)."""
+    ctx = md.ctx
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(tc.hp)
+    g = np.zeros(len(hpa))
+    val = ctypes.c_double(0.0)
+    ctx.check(lib.gpr_loo_grad(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(tc.Kinv),
+                               md.n, _ptr(tc.alpha), eps, crit, 1 if log_scale else 0,
+                               ctypes.byref(val) if want_value else None,
+                               g.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "gpr_loo_grad")
+    return g, (val.value if want_value else None)
+
+
+def _loo_loss(cost: LeaveOneOut, hp_or_md, md, tc, eps) -> float:
+    crit = _loo_crit(cost)
+    if isinstance(md, (MllLossCache, LooLossCache)):  # loss(LOO, md, tc): an up-to-date cache
+        return _loo_value(hp_or_md, _loo_cache_check(md, False), crit)
+    if md is None:
+        md, hp = hp_or_md, hp_or_md.params
+    else:
+        hp = hp_or_md
+    tc = LooLossCache(md) if tc is None else _loo_cache_check(tc, False)
+    update_cache_(tc, hp, md, eps)
+    return _loo_value(md, tc, crit)
+
+
+def _loo_loss_grad(cost: LeaveOneOut, F, G, hp, md: GPRModel, tc, eps, log_scale: bool):
+    crit = _loo_crit(cost)
+    _loo_cache_check(tc, True)
+    update_cache_(tc, hp, md, eps)
+    if G is not None:
+        g, val = _loo_grad(md, tc, crit, eps, log_scale, want_value=F is not None)
+        G[:] = g
+        return val
+    if F is not None:
+        return _loo_value(md, tc, crit)
+
+
 def loss(cost, hp_or_md, md: Optional[GPRModel] = None, tc: Optional[MllLossCache] = None,
          eps: float = EPS_DEFAULT) -> float:
     """loss(MLL, md) / loss(MLL, hp, md) / loss(MLL, hp, md, tc) (src/cost.jl:17-22,40-43);
-    loss(MLL, md, tc) reads the value off a cache that is already up to date."""
+    loss(MLL, md, tc) reads the value off a cache that is already up to date.  The same forms
+    with LeaveOneOut(...): tc a LooLossCache (the default) or an MllGradCache."""
+    if isinstance(cost, LeaveOneOut):
+        return _loo_loss(cost, hp_or_md, md, tc, eps)
     if isinstance(md, MllLossCache):
         # loss(MLL, md, tc): the value from an up-to-date cache (update_cache_ or append_ made
         # it), nothing refitted
@@ -564,7 +691,12 @@ def loss(cost, hp_or_md, md: Optional[GPRModel] = None, tc: Optional[MllLossCach
 
 def grad_(dL: np.ndarray, cost, hp, md: GPRModel, tc: Optional[MllGradCache] = None,
           eps: float = EPS_DEFAULT):
-    """grad!(dL, MLL, hp, md[, tc]) (src/cost.jl:32-36,45-48,119-126)."""
+    """grad!(dL, MLL, hp, md[, tc]) (src/cost.jl:32-36,45-48,119-126); with LeaveOneOut(...)
+    the criterion's gradient from the same MllGradCache."""
+    if isinstance(cost, LeaveOneOut):
+        _loo_crit(cost)  # (refused before a cache is allocated)
+        _loo_loss_grad(cost, None, dL, hp, md, MllGradCache(md) if tc is None else tc, eps, False)
+        return
     tc = tc or MllGradCache(md)
     update_cache_(tc, hp, md, eps)
     dL[:] = _mll_grad(md, tc, eps)
@@ -587,6 +719,8 @@ def grad(cost_or_cov, *args, **kw):
 
 def loss_grad_(cost, F, G, hp, md: GPRModel, tc: MllGradCache, eps: float = EPS_DEFAULT):
     """loss_grad!(cost, F, G, hp, md, tc) (src/cost.jl:50-58)."""
+    if isinstance(cost, LeaveOneOut):
+        return _loo_loss_grad(cost, F, G, hp, md, tc, eps, False)
     update_cache_(tc, hp, md, eps)
     if G is not None:
         G[:] = _mll_grad(md, tc, eps)
@@ -598,6 +732,8 @@ def log_loss_grad_(cost, F, G, log_hp, md: GPRModel, tc: MllGradCache, eps: floa
     """log_loss_grad!(cost, F, G, log_hp, md, tc) (src/cost.jl:60-70): hp = exp(log_hp),
     G .*= hp."""
     hp = np.exp(np.asarray(log_hp, dtype=np.float64))
+    if isinstance(cost, LeaveOneOut):
+        return _loo_loss_grad(cost, F, G, hp, md, tc, eps, True)
     update_cache_(tc, hp, md, eps)
     if G is not None:
         G[:] = _mll_grad(md, tc, eps, log_scale=True)
@@ -805,14 +941,22 @@ def split_factors(cov: AbstractKernel, hp, x, cm: Cmap, part: int = 0,
 # Cache constructors and small API pieces the reference exports around the path
 # =========================================================================================
 def loss_cache(cost):
-    """loss_cache(::MarginalLikelihood) = MllLossCache (src/cost.jl:10)."""
+    """loss_cache(::MarginalLikelihood) = MllLossCache (src/cost.jl:10); LeaveOneOut:
+    LooLossCache."""
+    if isinstance(cost, LeaveOneOut):
+        _loo_crit(cost)
+        return LooLossCache
     if not isinstance(cost, MarginalLikelihood):
         raise TypeError(f"no loss cache for {cost!r}")
     return MllLossCache
 
 
 def grad_cache(cost):
-    """grad_cache / loss_grad_cache(::MarginalLikelihood) = MllGradCache (src/cost.jl:11-12)."""
+    """grad_cache / loss_grad_cache(::MarginalLikelihood) = MllGradCache (src/cost.jl:11-12);
+    LeaveOneOut takes the same cache (K^{-1} and alpha are all its gradient reads)."""
+    if isinstance(cost, LeaveOneOut):
+        _loo_crit(cost)
+        return MllGradCache
     if not isinstance(cost, MarginalLikelihood):
         raise TypeError(f"no gradient cache for {cost!r}")
     return MllGradCache

@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import core as C
-from ._lib import GPR_COST_CHISQ, GPR_COST_MAHALANOBIS, GPR_COST_MSE, lib
+from ._lib import GPR_COST_CHISQ, GPR_COST_LOGPRED, GPR_COST_MAHALANOBIS, GPR_COST_MSE, lib
 
 
 class MSE:
@@ -34,6 +34,14 @@ class Mahalanobis:
     """loss(::Mahalanobis, y, yp, Sigma_p) = ||L^{-1}(y - yp)||^2 with Sigma_p = L L^T
     (src/loss_grad.jl:25-30)."""
     COST = GPR_COST_MAHALANOBIS
+
+
+class LogPredictive:
+    """The negative log predictive density of one held-out point, 0.5 log var + (y - yp)^2 /
+    (2 var) + 0.5 log 2pi (Rasmussen & Williams eq. 5.10).  A leave-one-out criterion only
+    (``LeaveOneOut(LogPredictive())``, its default): it carries no ``COST``, so ``cv_batch`` and
+    ``cv_kfold`` refuse it like any other object."""
+    LOO_CRIT = GPR_COST_LOGPRED
 
 
 def _cost_code(cost) -> int:

@@ -7,8 +7,8 @@ LogScale optimisation in log space) and src/update_model.jl:1-100 (``update_samp
 
 Every loss / gradient evaluation runs on the GPU through libgpr_hip.so (K-assembly, POTRF,
 POTRS, POTRI and the fused gradient of core.update_cache_ / core._mll_grad) on ONE
-MllGradCache kept resident for the whole optimisation: per iteration only the D
-hyper-parameters go down and the loss and D gradient components come back.  The optimiser
+cache (the cost's loss_grad_cache, or its loss_cache for a zeroth-order method) kept resident
+for the whole optimisation: per iteration only the D hyper-parameters go down and the loss and D gradient components come back.  The optimiser
 itself is host control logic: the reference uses Optim.jl (not vendored, Manifest.toml), here
 SciPy's ``optimize.minimize`` with the matching algorithm family stands in for it (CG for
 ConjugateGradient, L-BFGS-B for LBFGS, BFGS, Nelder-Mead, and trust-exact with the
@@ -111,7 +111,7 @@ class _Objective:
 
     def __init__(self, cost, md: C.GPRModel, log: bool, need_grad: bool):
         self.cost, self.md, self.log = cost, md, log
-        self.tc = C.MllGradCache(md) if need_grad else C.MllLossCache(md)
+        self.tc = (C.loss_grad_cache(cost) if need_grad else C.loss_cache(cost))(md)
         self.f_calls = self.g_calls = 0
         self._x = None
         self._f = None

@@ -132,6 +132,9 @@ extern "C" {
 #define GPR_COST_MSE 1         /* MSE:  sum((y - yp)^2) / length(y)                   */
 #define GPR_COST_CHISQ 2       /* ChiSq: sum((y - yp)^2 / Sigma_p[i, i])              */
 #define GPR_COST_MAHALANOBIS 3 /* Mahalanobis: ||L^{-1}(y - yp)||^2, Sigma_p = L L^T   */
+/* leave-one-out only (gpr_loo, gpr_loo_grad; gpr_cv_batch / gpr_cv_kfold refuse it): the negative
+ * log predictive density, 0.5 log var + (y - yp)^2 / (2 var) + 0.5 log 2pi  (R&W eq. 5.10) */
+#define GPR_COST_LOGPRED 4
 
 typedef struct gpr_ctx* gpr_ctx_t;
 
@@ -161,7 +164,10 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *        that makes its Q (call-level: the launches inside it also count in their own classes),
  *        11 the append's skinny solve (V = U^{-T} K(x, x_new) of gpr_fit_append, whichever route
  *        takes it; call-level too; the flops slot carries n0^2 m), 12 the rank-r update of
- *        gpr_fit_remove (its W rows and every launch of either route; call-level).
+ *        gpr_fit_remove (its W rows and every launch of either route; call-level), 13 / 14 the
+ *        fold Grams / per-fold solves of gpr_cv_kfold, 15 the small kernels of the leave-one-out
+ *        entries (diag K^{-1}, per-point terms, b = P f_alpha, row scaling, pre-fill, mirror),
+ *        16 gpr_loo_grad's SYRK (call-site class; the flops slot carries n^2 (n + 1)).
  *        Returns accumulated ms, launch count, flops (bytes for class 0). */
 /* Knobs: the library's run-time switches.  Each is a GPR_* environment variable read ONCE,
  * when a context is created, and can be changed on a live context with gpr_set_knob (values
@@ -539,6 +545,47 @@ int gpr_cv_batch(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
 int gpr_cv_kfold(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                  const double* dX, int n, const double* dy, const int* tst, int ntst, int nfold,
                  int cost, double eps, double* lss, double* mu, double* var);
+
+/* ---- leave-one-out training criteria (no counterpart in the reference, which ships only
+ * MarginalLikelihood on its AbstractLoss seam, src/cost.jl) ------------------------------- */
+/* With K the GPR_SELF matrix of all n points, P = K^{-1} and alpha = K^{-1} y (gpr_cv_kfold's
+ * identities for one-point folds: yp_i = y_i - alpha_i / P_ii, var_i = 1 / P_ii) a criterion is
+ * L = sum_i f(alpha_i, P_ii), crit one of
+ *   GPR_COST_LOGPRED      f = -0.5 log P_ii + alpha_i^2 / (2 P_ii) + 0.5 log 2pi
+ *   GPR_COST_MSE          f = (alpha_i / P_ii)^2
+ *   GPR_COST_CHISQ        f = alpha_i^2 / P_ii      (GPR_COST_MAHALANOBIS on one point: the same)
+ * the last three the SUM (not the mean) over the n one-point folds of gpr_cv_kfold's losses.
+ *
+ * One-call fit for the value alone: dK (n x n, ldk) <- kernel, in-place POTRF (upper U, strict
+ * lower K, as gpr_fit), dalpha <- K^{-1} dy (one column), dpdiag[n] (device) <- diag(K^{-1}) as
+ * the column norms of Z = U^{-T}, P_ii = sum_{k >= i} Z_ki^2: no Gram of Z is formed.  Z rides in
+ * the factorisation as in gpr_fit_kinv (device workspace: n^2 doubles).  The front half of
+ * gpr_cv_kfold.  Returns info > 0 if not PD; synchronises.  GPR_E_ARG as below. */
+int gpr_fit_loo(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                const double* dX, int n, const double* dy, double eps, double* dK, int ldk,
+                double* dalpha, double* dpdiag, int* info);
+
+/* *out = L for crit, from alpha and P_ii = dp[i * incp]: incp = 1 reads gpr_fit_loo's dpdiag,
+ * incp = ldkinv + 1 the diagonal of gpr_fit_kinv's dKinv.  One launch, the sum in a fixed order. */
+int gpr_loo(gpr_ctx_t ctx, int crit, const double* dp, int incp, const double* dalpha, int n,
+            double* out);
+
+/* grad[D] (host) of L w.r.t. hp and, where value is not NULL, *value = L, from what gpr_fit_kinv
+ * left: dKinv (n x n, ldk, symmetric in full) and dalpha are read only.  With b = P f_alpha,
+ * s_i = sqrt(-f_P,i) (f_P <= 0 for every criterion) and S = diag(s) P:
+ *   dL/dtheta_j = -sum_ab dK_j,ab [ 0.5 (b_a alpha_b + alpha_a b_b) - (S^T S)_ab ]
+ * (R&W eq. 5.13 summed over the points; they quote O(n^3) PER hyper-parameter).  Here: the
+ * per-point terms, b (one pass over P), S, then M = 2 S^T S - (b alpha^T + alpha b^T) on the
+ * upper triangle by ONE SYRK on the pipelined FP64 MFMA GEMM, and the fused pass of gpr_mll_grad
+ * with a = 0 and M in K^{-1}'s place -- all D components of every kind of part for one extra n^3
+ * product.  log_scale != 0 applies G .*= hp.  Device workspace: two n^2 buffers of the context (S
+ * where gpr_fit_kinv kept Z, and M).  Every sum in a fixed order: two calls on the same inputs
+ * agree bit for bit.  Synchronises.
+ * GPR_E_ARG for a NULL pointer other than value, n < 1, ldk < n, incp < 1 or an unknown crit:
+ * the message names the argument, nothing is written. */
+int gpr_loo_grad(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                 const double* dX, int n, const double* dKinv, int ldk, const double* dalpha,
+                 double eps, int crit, int log_scale, double* value, double* grad);
 
 /* integrate(md, hp, a, b; sample_noise = noise::Vector) (src/integrate.jl:71-100,149-162):
  * per column j of y (ny columns, noise[j] host), Iout[j] = k1' (K + noise_j I)^{-1} y_j and
