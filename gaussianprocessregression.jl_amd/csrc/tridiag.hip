@@ -1364,7 +1364,8 @@ const void* trd_kernel_ptr() {
 // Returns GPR_E_UNSUP -- before touching B -- when n is beyond the bound or the launch's
 // workgroups cannot all be resident at once (the exchange needs every one of them every step:
 // the launch is cooperative, so the runtime refuses it up front rather than letting resident
-// workgroups spin on absent ones); the callers then take another route.
+// workgroups spin on absent ones); the callers then take another route.  Only a process that
+// the device grants no cooperative queue at all launches the same grid the ordinary way.
 int sym_tridiag(gpr_ctx* ctx, const double* dA, int n, int lda, double* dB, int m, int ldb,
                 double* dd, double* de) {
   if (n <= 0) return 0;
@@ -1502,11 +1503,21 @@ int sym_tridiag(gpr_ctx* ctx, const double* dA, int n, int lda, double* dB, int 
   // cooperative: all P workgroups resident together, or the runtime refuses the launch (nothing
   // has run then: B is untouched, and the caller falls back)
   void* kargs[] = {&a};
-  if (hipLaunchCooperativeKernel(kfn, dim3(P), dim3(TRD_THREADS), kargs, (unsigned)shmem, st) !=
-      hipSuccess) {
+  hipError_t lerr =
+      hipLaunchCooperativeKernel(kfn, dim3(P), dim3(TRD_THREADS), kargs, (unsigned)shmem, st);
+  if (lerr != hipSuccess && lerr != hipErrorCooperativeLaunchTooLarge) {
+    // refused for another reason than the grid's size: the process has no cooperative queue (a
+    // virtualised device grants it to one process at a time -- hipErrorIllegalState in every
+    // other).  The kernels synchronise by their polls alone, and the grid fits the device by the
+    // check above (P <= CUs, one workgroup each), so an ordinary launch is co-resident as soon
+    // as other work leaves the CUs; the waits stay bounded (a time-out is reported below).
     (void)hipGetLastError();
-    return set_err(ctx, GPR_E_UNSUP, "tridiagonal reduction: cooperative launch of %d workgroups "
-                   "refused", P);
+    lerr = hipLaunchKernel(kfn, dim3(P), dim3(TRD_THREADS), kargs, shmem, st);
+  }
+  if (lerr != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(ctx, GPR_E_UNSUP, "tridiagonal reduction: launch of %d workgroups refused (%s)",
+                   P, hipGetErrorName(lerr));
   }
   int herr = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, st));

@@ -630,7 +630,9 @@ int gpr_syev_apply(gpr_ctx_t ctx, const double* dA, int n, int lda, double* dB, 
  * <- Q^T dB.  One persistent launch (the unblocked two-sided Householder reduction, columns
  * dealt round-robin over the CUs; for m <= 1024 Q^T B is formed inside it), else the
  * back-transform by 64-reflector blocks on the MFMA GEMM.  The launch is cooperative (every
- * workgroup resident or refused up front: GPR_E_UNSUP, nothing touched); below n = 5376 its
+ * workgroup resident or refused up front: GPR_E_UNSUP, nothing touched; a process to which the
+ * device grants no cooperative queue -- a virtualised device has one, for one process at a
+ * time -- launches the same grid, which fits the device, the ordinary way); below n = 5376 its
  * step vectors sit in LDS and every step updates every trailing column; from 5376 on the
  * updates are deferred by panels of 16 steps (later columns only read per step, flushed per
  * panel by an MFMA GEMM).  n <= 16384 (GPR_E_UNSUP beyond). */
