@@ -1,0 +1,279 @@
+// K^{-1} B without K: conjugate gradients on the matrix gpr_fit factors (the GPR_SELF form: eps
+// per term and sigma_n^2 on the diagonal), every product K P by the matrix-free kernel
+// (kmatmul.hip), so a model with more points than an n x n buffer allows still gets its weights.
+//
+// The nrhs columns are independent recurrences that share one product per iteration; a column
+// whose residual has met the stop test is frozen (x, r, p keep their values) while the others go
+// on.  K's diagonal is constant (the terms' sigma^2 products + eps each + sigma_n^2), so Jacobi
+// scaling is a scalar: z = r / diag.  It is the only preconditioning.
+// Per iteration, after Q = K P:
+//   cg_dot_kernel     partial sums of p.q per column, one per 256-thread block (each thread a
+//                     fixed stride of rows, then a fixed tree) -- stage one
+//   cg_step_xr_kernel every block sums the column's partials in the same fixed tree (stage two),
+//                     alpha = (r.r / diag) / p.q, x += alpha p, r -= alpha q, partials of r.r
+//   cg_step_p_kernel  the same second stage for r.r, beta = r.r / (previous r.r), p = r / diag +
+//                     beta p; block 0 writes the column's r.r and its frozen flag for the next
+//                     iteration into the other of two scalar slots (nobody reads that slot in
+//                     this launch)
+// No atomics: two calls agree bit for bit.  alpha and beta never leave the device; the host reads
+// the nrhs values of r.r once per iteration for the stop test ||r_c|| <= tol ||b_c||.
+// At the end relres is the TRUE residual ||b - K x|| / ||b|| from one more product, not the
+// recurrence's.
+//
+// Limits.  Memory is O(n nrhs): r, p, q (3 n nrhs doubles) beside the product's linear
+// workspace.  The iteration count is governed by sqrt(cond_2(K)) -- about 0.5 sqrt(cond) ln(2 /
+// tol) -- and cond_2 <= 1 + n sigma^2 / sigma_n^2: small noise means many iterations, each a full
+// evaluation of K.  A low-rank preconditioner is the remedy and is not part of this file.
+// Reaching maxit is not an error.
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+
+namespace {
+
+constexpr int CG_MAXB = 256;  // most partial sums (blocks) per column
+
+// sum of the 256 threads' values by a fixed tree; every thread gets it
+__device__ __forceinline__ double cg_block_sum(double v, double* red) {
+  __syncthreads();  // red's previous use is over
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// the scalars of one column, slot s of two: sc[(s * nrhs + c) * 2 + {0: r.r, 1: frozen}]; bb[c]
+__host__ __device__ inline double* cg_slot(double* sc, int s, int nrhs, int c) {
+  return sc + ((size_t)s * nrhs + c) * 2;
+}
+
+// grid (nblk, nrhs).  x = 0, r = b, p = b / diag; part[c][blk] = partial b.b
+__global__ __launch_bounds__(256) void cg_init_kernel(const double* __restrict__ B, size_t ldb,
+                                                      int n, double dinv, double* __restrict__ X,
+                                                      size_t ldx, double* __restrict__ R,
+                                                      double* __restrict__ P,
+                                                      double* __restrict__ part) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  double s = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double b = B[(size_t)c * ldb + i];
+    X[(size_t)c * ldx + i] = 0.0;
+    R[(size_t)c * n + i] = b;
+    P[(size_t)c * n + i] = b * dinv;
+    s = fma(b, b, s);
+  }
+  s = cg_block_sum(s, red);
+  if (threadIdx.x == 0) part[(size_t)c * CG_MAXB + blockIdx.x] = s;
+}
+
+// grid nrhs.  bb[c] = b.b; slot 0: r.r = b.b, frozen when b = 0 (x = 0 is the solution)
+__global__ __launch_bounds__(256) void cg_init_scalars_kernel(const double* __restrict__ part,
+                                                              int nblk, int nrhs, double tol2,
+                                                              double* __restrict__ sc,
+                                                              double* __restrict__ bb) {
+  __shared__ double red[256];
+  const int c = blockIdx.x;
+  const double s =
+      cg_block_sum((int)threadIdx.x < nblk ? part[(size_t)c * CG_MAXB + threadIdx.x] : 0.0, red);
+  if (threadIdx.x == 0) {
+    bb[c] = s;
+    double* o = cg_slot(sc, 0, nrhs, c);
+    o[0] = s;
+    o[1] = s <= tol2 * s ? 1.0 : 0.0;  // (only b = 0, or tol >= 1)
+  }
+}
+
+// grid (nblk, nrhs).  part[c][blk] = partial sum_i u_i v_i (u, v: n x nrhs, ld n)
+__global__ __launch_bounds__(256) void cg_dot_kernel(const double* __restrict__ U,
+                                                     const double* __restrict__ V, int n,
+                                                     double* __restrict__ part) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  double s = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    s = fma(U[(size_t)c * n + i], V[(size_t)c * n + i], s);
+  s = cg_block_sum(s, red);
+  if (threadIdx.x == 0) part[(size_t)c * CG_MAXB + blockIdx.x] = s;
+}
+
+// grid (nblk, nrhs).  alpha = (r.r dinv) / p.q from pq's partials; x += alpha p, r -= alpha q;
+// rr[c][blk] = partial r.r of the new r.  A frozen column is left alone.
+__global__ __launch_bounds__(256) void cg_step_xr_kernel(
+    const double* __restrict__ pq, int nblk, int nrhs, int slot, double* __restrict__ sc,
+    double dinv, int n, const double* __restrict__ P, const double* __restrict__ Q,
+    double* __restrict__ X, size_t ldx, double* __restrict__ R, double* __restrict__ rr) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const double* cur = cg_slot(sc, slot, nrhs, c);
+  if (cur[1] != 0.0) return;  // (block-uniform)
+  const double den =
+      cg_block_sum((int)threadIdx.x < nblk ? pq[(size_t)c * CG_MAXB + threadIdx.x] : 0.0, red);
+  const double alpha = (cur[0] * dinv) / den;
+  double s = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const size_t k = (size_t)c * n + i;
+    X[(size_t)c * ldx + i] = fma(alpha, P[k], X[(size_t)c * ldx + i]);
+    const double r = fma(-alpha, Q[k], R[k]);
+    R[k] = r;
+    s = fma(r, r, s);
+  }
+  s = cg_block_sum(s, red);
+  if (threadIdx.x == 0) rr[(size_t)c * CG_MAXB + blockIdx.x] = s;
+}
+
+// grid (nblk, nrhs).  beta = r.r / previous r.r; p = r dinv + beta p; block 0 fills the other
+// slot: the new r.r and frozen = r.r <= tol^2 b.b.  A frozen column carries its slot over.
+__global__ __launch_bounds__(256) void cg_step_p_kernel(
+    const double* __restrict__ rr, int nblk, int nrhs, int slot, double* __restrict__ sc,
+    const double* __restrict__ bb, double tol2, double dinv, int n, const double* __restrict__ R,
+    double* __restrict__ P) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const double* cur = cg_slot(sc, slot, nrhs, c);
+  double* nxt = cg_slot(sc, slot ^ 1, nrhs, c);
+  if (cur[1] != 0.0) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      nxt[0] = cur[0];
+      nxt[1] = 1.0;
+    }
+    return;
+  }
+  const double num =
+      cg_block_sum((int)threadIdx.x < nblk ? rr[(size_t)c * CG_MAXB + threadIdx.x] : 0.0, red);
+  const double beta = num / cur[0];
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const size_t k = (size_t)c * n + i;
+    P[k] = fma(beta, P[k], R[k] * dinv);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    nxt[0] = num;
+    nxt[1] = num <= tol2 * bb[c] ? 1.0 : 0.0;
+  }
+}
+
+// grid (nblk, nrhs).  part[c][blk] = partial ||b - q||^2
+__global__ __launch_bounds__(256) void cg_resid_kernel(const double* __restrict__ B, size_t ldb,
+                                                       const double* __restrict__ Q, int n,
+                                                       double* __restrict__ part) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  double s = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double r = B[(size_t)c * ldb + i] - Q[(size_t)c * n + i];
+    s = fma(r, r, s);
+  }
+  s = cg_block_sum(s, red);
+  if (threadIdx.x == 0) part[(size_t)c * CG_MAXB + blockIdx.x] = s;
+}
+
+// grid nrhs.  out[c] = the sum of the column's partials
+__global__ __launch_bounds__(256) void cg_sum_kernel(const double* __restrict__ part, int nblk,
+                                                     double* __restrict__ out) {
+  __shared__ double red[256];
+  const int c = blockIdx.x;
+  const double s =
+      cg_block_sum((int)threadIdx.x < nblk ? part[(size_t)c * CG_MAXB + threadIdx.x] : 0.0, red);
+  if (threadIdx.x == 0) out[c] = s;
+}
+
+// K's constant diagonal in the GPR_SELF form
+double cg_diagonal(const KParams& kp) {
+  double dg = kp.has_noise ? kp.noise2 : 0.0, term = 1.0;
+  for (int p = 0; p < kp.nse; ++p) {
+    const double s = kp_sigma(kp, p);
+    term *= s * s;
+    if (kp_closes(kp, p)) {
+      dg += term + kp.eps;
+      term = 1.0;
+    }
+  }
+  return dg;
+}
+
+struct PinnedDoubles {  // the stop test's host copy
+  double* p = nullptr;
+  ~PinnedDoubles() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                 const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
+                 double tol, int maxit, double* dXout, int ldx, int* iters, double* relres) {
+  KParams kp;
+  GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, nullptr));
+  if (!dX) return set_err(ctx, GPR_E_ARG, "dX is NULL");
+  if (!dB) return set_err(ctx, GPR_E_ARG, "dB is NULL");
+  if (!dXout) return set_err(ctx, GPR_E_ARG, "dXout is NULL");
+  if (n < 1) return set_err(ctx, GPR_E_ARG, "n=%d < 1", n);
+  if (nrhs < 1) return set_err(ctx, GPR_E_ARG, "nrhs=%d < 1", nrhs);
+  if (ldb < n) return set_err(ctx, GPR_E_ARG, "ldb=%d < n=%d", ldb, n);
+  if (ldx < n) return set_err(ctx, GPR_E_ARG, "ldx=%d < n=%d", ldx, n);
+  if (!(tol > 0.0)) return set_err(ctx, GPR_E_ARG, "tol=%g is not positive", tol);
+  if (maxit < 0) return set_err(ctx, GPR_E_ARG, "maxit=%d < 0", maxit);
+  const double dinv = 1.0 / cg_diagonal(kp), tol2 = tol * tol;
+  const size_t nn = (size_t)n * nrhs, np = (size_t)nrhs * CG_MAXB;
+  // r | p | q | p.q partials | r.r partials | two scalar slots | b.b | the final residuals
+  GPR_TRY(ensure_buf(ctx, ctx->dcg, 3 * nn + 2 * np + 6 * (size_t)nrhs));
+  double* R = ctx->dcg;
+  double *P = R + nn, *Q = P + nn, *pq = Q + nn, *rr = pq + np, *sc = rr + np;
+  double *bb = sc + 4 * (size_t)nrhs, *res = bb + nrhs;
+  PinnedDoubles host;
+  HIP_TRY(ctx, hipHostMalloc((void**)&host.p, sizeof(double) * 2 * nrhs, hipHostMallocDefault));
+  KmmOps ops;
+  GPR_TRY(kmm_prepare(ctx, kp, dX, n, nullptr, n, GPR_SELF, &ops));
+  const int nblk = std::max(1, std::min(CG_MAXB, (n + 1023) / 1024));
+  const dim3 grid((unsigned)nblk, (unsigned)nrhs);
+  hipStream_t st = ctx->stream;
+  cg_init_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, n, dinv, dXout, (size_t)ldx, R, P, rr);
+  cg_init_scalars_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, nrhs, tol2, sc, bb);
+  LAUNCH_CHECK(ctx);
+  // the stop test reads the slot's (r.r, frozen) pairs: every column frozen
+  auto all_frozen = [&](int slot, bool* done) {
+    HIP_TRY(ctx, hipMemcpyAsync(host.p, cg_slot(sc, slot, nrhs, 0), sizeof(double) * 2 * nrhs,
+                                hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *done = true;
+    for (int c = 0; c < nrhs; ++c)
+      if (host.p[2 * c + 1] == 0.0) *done = false;
+    return 0;
+  };
+  int it = 0;
+  bool done = false;
+  GPR_TRY(all_frozen(0, &done));
+  while (!done && it < maxit) {
+    const int slot = it & 1;
+    GPR_TRY(kmm_apply(ctx, ops, P, nrhs, n, Q, n));
+    cg_dot_kernel<<<grid, 256, 0, st>>>(P, Q, n, pq);
+    cg_step_xr_kernel<<<grid, 256, 0, st>>>(pq, nblk, nrhs, slot, sc, dinv, n, P, Q, dXout,
+                                            (size_t)ldx, R, rr);
+    cg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, nrhs, slot, sc, bb, tol2, dinv, n, R, P);
+    LAUNCH_CHECK(ctx);
+    ++it;
+    GPR_TRY(all_frozen(it & 1, &done));
+  }
+  if (iters) *iters = it;
+  if (relres) {  // the true residual
+    GPR_TRY(kmm_apply(ctx, ops, dXout, nrhs, ldx, Q, n));
+    cg_resid_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, Q, n, rr);
+    cg_sum_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, res);
+    LAUNCH_CHECK(ctx);
+    // (bb and res are adjacent: one copy)
+    HIP_TRY(ctx, hipMemcpyAsync(host.p, bb, sizeof(double) * 2 * nrhs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (int c = 0; c < nrhs; ++c)
+      relres[c] = host.p[c] > 0.0 ? std::sqrt(host.p[nrhs + c] / host.p[c]) : 0.0;
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -326,6 +326,11 @@ struct gpr_ctx {
   DevBuf dgA;                   // Gram-assembly row operands (MFMA lane order, assembly.hip)
   DevBuf dgB;                   // Gram-assembly column operands
   DevBuf dgc;                   // Gram-assembly centres (nse x d)
+  DevBuf dkmm;                  // matrix-free product: slab partials (kmatmul.hip)
+  DevBuf dcg;                   // conjugate gradients: r, p, K p, partial sums, scalars (cg.hip)
+  int kmm_slabs = 0;            // GPR_KMM_SLABS: slabs of xb per 64 output points (0 auto)
+  int mean_free = -1;           // GPR_MEAN_FREE: gpr_predict's mean without K(x, xp) (1), with it
+                                // (0), -1 auto: matrix-free when no dwork is passed and n m > 2^29
   // upper-only K assembly for a factorisation (assembly.hip kmat_symu_kernel): its work list
   // (strip << 16 | segment, built once per n); the matrix it last left without its strict
   // lower off-diagonal tiles is fc's kup claim -- the next potrf_core on exactly that matrix has
@@ -487,6 +492,24 @@ int launch_kernel_matrix_for_factor(gpr_ctx* ctx, const KParams& kp, const doubl
                                     double* dK, int ldk);
 int launch_mirror_upper(gpr_ctx* ctx, double* A, int n, int lda);
 int launch_scale_inputs(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, double* out);
+// buf (grown to nse x de x n doubles) <- the per-part scaled points as the K assembly takes them
+// (2d-wide embedded features when the description has a Periodic part)
+int launch_scaled_points(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, DevBuf& buf);
+// kmatmul.hip: Out (na x nv, ldo) = K(xa, xb) V, K never stored.  kmm_prepare scales the points
+// and prepares the Gram operands once (in ctx->dxs / dxps / dgA / dgB / dgc, valid until the
+// next call that builds a kernel matrix on the context); kmm_apply multiplies, any number of
+// times.  same: GPR_CROSS / GPR_SELF / GPR_SAME_OBJECT (na == nb, xb ignored).
+struct KmmOps {
+  KParams kp;  // the feature view, has_noise as the form asks
+  int na, nb, same, S;
+  const double *xa, *xb;  // scaled points (all parts)
+  const double *A, *nrmA, *B, *nrmB;
+  int nbA, nbB;
+};
+int kmm_prepare(gpr_ctx* ctx, const KParams& kp, const double* dXa, int na, const double* dXb,
+                int nb, int same, KmmOps* o);
+int kmm_apply(gpr_ctx* ctx, const KmmOps& o, const double* dV, int nv, int ldv, double* dOut,
+              int ldo);
 // ctx->dxs <- per part and point [cos(2 pi x_k / p_k) | sin(2 pi x_k / p_k)] (2d wide, without
 // l_k) for the Periodic parts of kp (the other parts' rows are not for use); the MLL gradient's
 // per-point table

@@ -295,6 +295,16 @@ int gpr_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d
     return set_err(ctx, GPR_E_ARG, "bad args");
   if (mode != GPR_PREDICT_MEAN && !dvar) return set_err(ctx, GPR_E_ARG, "dvar is NULL");
   if (mode == GPR_PREDICT_FULL && ldv < m) return set_err(ctx, GPR_E_ARG, "ldv < m");
+  // The mean alone needs no K(x, xp): mu = K(xp, x) wt by the matrix-free product (kmatmul.hip),
+  // whose memory is linear in n + m.  GPR_MEAN_FREE: 1 always, 0 never; by default only where
+  // the scratch it replaces would pass 4 GiB and the caller passed none.
+  if (mode == GPR_PREDICT_MEAN &&
+      (ctx->mean_free > 0 || (ctx->mean_free < 0 && !dwork && (size_t)n * m > ((size_t)1 << 29)))) {
+    KmmOps ops;
+    GPR_TRY(kmm_prepare(ctx, kp, dXp, m, dX, n, dXp == dX && m == n ? GPR_SAME_OBJECT : GPR_CROSS,
+                        &ops));
+    return kmm_apply(ctx, ops, dwt, nrhs, n, dmu, m);
+  }
   double* Kpx = dwork;
   if (!Kpx) {
     GPR_TRY(ensure_buf(ctx, ctx->dbig2, (size_t)n * m));

@@ -37,6 +37,7 @@ from .core import (
     grad_,
     islog,
     kernel,
+    kernel_matmul,
     log_loss_grad_,
     loss,
     loss_grad_,
@@ -48,6 +49,8 @@ from .core import (
     predict_grad_,
     predict_mean,
     predict_mean_,
+    predict_mean_from,
+    solve_cg,
     split_factors,
     update_cache_,
     update_predict_cache_,

@@ -426,6 +426,38 @@ def kernel(cov: AbstractKernel, hp, x, xp=None, eps: float = EPS_DEFAULT,
     return ctx.host(K) if host else K
 
 
+def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAULT,
+                  ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                  host: bool = True):
+    """kernel(cov, hp, x, xp) @ V without the matrix: the N x M kernel is evaluated tile by tile in
+    registers (gpr_kernel_matmul), so memory stays linear in N + M.  ``xp`` selects the form by
+    kernel()'s rule (None: eps per stationary part plus noise, the matrix a fit factors; ``xp is
+    x``: eps, no noise; else a cross kernel).  V: M or M x nv.  A device V is column-major with
+    its rows as the leading dimension (nv x ldv tensor, ldv >= M), and so is ``out`` (nv x ldo,
+    ldo >= N), which is then returned as it is."""
+    ctx = ctx or default_context()
+    dx = ctx.colmajor(x)
+    n = dx.shape[0]
+    d = dx.shape[1] if dx.ndim == 2 else 1
+    kinds, nk = _kinds_arr(cov)
+    hpa, hpp = _hp_arr(hp)
+    if xp is None:
+        m, dxp, same = n, None, _lib.GPR_SELF
+    elif xp is x:
+        m, dxp, same = n, None, _lib.GPR_SAME_OBJECT
+    else:
+        dxp = ctx.colmajor(xp)
+        m, same = dxp.shape[0], _lib.GPR_CROSS
+    dV = ctx.colmajor(V)
+    vec = dV.ndim == 1
+    nv = 1 if vec else dV.shape[0]
+    O = out if out is not None else (ctx.empty(n) if vec else ctx.empty(nv, n))
+    ctx.check(lib.gpr_kernel_matmul(ctx.h, kinds, nk, hpp, d, _ptr(dx), n, _ptr(dxp), m, same, eps,
+                                    _ptr(dV), nv, dV.shape[-1], _ptr(O), O.shape[-1]),
+              "gpr_kernel_matmul")
+    return ctx.host(O) if host and out is None else O
+
+
 def kernel_grad(cov: AbstractKernel, i: int, hp, x, eps: float = EPS_DEFAULT,
                 ctx: Optional[Context] = None):
     """grad(cov, i, hp, x) (src/deriv_covar.jl:2-32): dK/dtheta_i, i is 1-based."""
@@ -794,25 +826,73 @@ def predict_(mu: Optional[torch.Tensor], Sigma: Optional[torch.Tensor], md: GPRM
     hpa, hpp = _hp_arr(md.params)
     dxp = _dxp(md, xp)
     m = dxp.shape[0]
-    if pc.Kxp.numel() < m * md.n:
+    free = mean_only and _mean_free(ctx, md.n, m)  # (no Kxp: the library gets no scratch)
+    if not free and pc.Kxp.numel() < m * md.n:
         pc.Kxp = ctx.empty(m, md.n)
     mode = (_lib.GPR_PREDICT_MEAN if mean_only else
             _lib.GPR_PREDICT_DIAG if diagonal_var else _lib.GPR_PREDICT_FULL)
     ldv = m
     ctx.check(lib.gpr_predict(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(pc.Kxx), pc.ld,
                               _ptr(pc.wt), pc.nrhs, _ptr(dxp), m, mode, eps, _ptr(mu), _ptr(Sigma),
-                              ldv, _ptr(pc.Kxp)), "gpr_predict")
+                              ldv, None if free else _ptr(pc.Kxp)), "gpr_predict")
+
+
+def _mean_free(ctx: Context, n: int, m: int) -> bool:
+    """Will gpr_predict's mean take the matrix-free route when it is given no scratch?  The knob
+    GPR_MEAN_FREE: 1 always, 0 never, unset only where K(x, xp) would pass 4 GiB (n m > 2^29)."""
+    mf = ctx.get_knob("GPR_MEAN_FREE")
+    return mf > 0 or (mf < 0 and n * m > 2 ** 29)
 
 
 def predict_mean(md: GPRModel, xp, eps: float = EPS_DEFAULT) -> np.ndarray:
     """predict_mean(md, xp) (src/predict.jl:6-12)."""
     ctx = md.ctx
     m = np.asarray(xp).shape[-1]
-    pc = GPRPredictCache(md, m)
+    pc = GPRPredictCache(md, 0 if _mean_free(ctx, md.n, m) else m)
     _update_predict_cache(pc, md, eps)
     mu = ctx.empty(pc.nrhs, m) if pc.nrhs > 1 else ctx.empty(m)
     predict_(mu, None, md, xp, pc, True, mean_only=True, eps=eps)
     return ctx.host(mu)
+
+
+def predict_mean_from(md: GPRModel, alpha, xp, eps: float = EPS_DEFAULT) -> np.ndarray:
+    """The posterior mean K(xp, x) alpha from given weights (N or N x ne, e.g. solve_cg's), by the
+    matrix-free product: no factorisation and no K(x, xp), so together with solve_cg it serves a
+    model whose kernel matrix was never formed.  ``xp is md.x`` follows predict's same-object
+    rule."""
+    ctx = md.ctx
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(md.params)
+    dxp = _dxp(md, xp)
+    m = dxp.shape[0]
+    da = ctx.colmajor(alpha)
+    nrhs = 1 if da.ndim == 1 else da.shape[0]
+    same = _lib.GPR_SAME_OBJECT if dxp is md.dx() else _lib.GPR_CROSS
+    mu = ctx.empty(nrhs, m) if da.ndim == 2 else ctx.empty(m)
+    ctx.check(lib.gpr_kernel_matmul(ctx.h, kinds, nk, hpp, md.d, _ptr(dxp), m, _ptr(md.dx()), md.n,
+                                    same, eps, _ptr(da), nrhs, da.shape[-1], _ptr(mu), m),
+              "gpr_kernel_matmul")
+    return ctx.host(mu)
+
+
+def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = None,
+             eps: float = EPS_DEFAULT):
+    """K^{-1} B by conjugate gradients on the matrix a fit factors, every product matrix-free
+    (gpr_solve_cg): memory O(N), no preconditioner beyond K's constant diagonal, iterations ~
+    sqrt(cond(K)).  B defaults to md.y; maxit to N.  Returns (alpha, iters, relres) with relres
+    the true ||b - K alpha|| / ||b|| per column; reaching maxit is reported, not raised."""
+    ctx = md.ctx
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(md.params)
+    dB = md.dy() if B is None else ctx.colmajor(B)
+    nrhs = 1 if dB.ndim == 1 else dB.shape[0]
+    X = ctx.empty(md.n) if dB.ndim == 1 else ctx.empty(nrhs, md.n)
+    iters = ctypes.c_int(0)
+    relres = (ctypes.c_double * nrhs)()
+    ctx.check(lib.gpr_solve_cg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB), nrhs,
+                               dB.shape[-1], eps, tol, md.n if maxit is None else int(maxit),
+                               _ptr(X), md.n, ctypes.byref(iters), relres), "gpr_solve_cg")
+    return ctx.host(X), iters.value, np.array(relres[:])
 
 
 def predict(md: GPRModel, xp, diagonal_var: bool = False, eps: float = EPS_DEFAULT,

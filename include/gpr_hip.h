@@ -240,6 +240,12 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         and one panel launch per 128-row block (0); -1 auto: the launch chain,
  *                         which measured faster at n0 = 32768 (r = 1 oldest: 16.1 vs 19.1 ms per update,
  *                         r = 128: 316 vs 427).  The two agree bit for bit
+ *   GPR_KMM_SLABS      0  gpr_kernel_matmul: slabs the summed points are cut into per 64 output
+ *                         points (each a workgroup; their partial products are added in slab
+ *                         order); 0 auto: the fewest that give two workgroups per CU, at most 64
+ *   GPR_MEAN_FREE     -1  gpr_predict, GPR_PREDICT_MEAN: the mean by the matrix-free product (1)
+ *                         or through K(x, xp) (0); -1 auto: matrix-free only when dwork is NULL
+ *                         and the scratch it replaces would pass 4 GiB (n m > 2^29)
  * A gpr_mgpu handle has knobs of its own, read from the environment once at gpr_mgpu_create
  * and changed with gpr_mgpu_set_knob / gpr_mgpu_get_knob (below):
  *   GPR_MGPU_STREAM   -1  1: stream U out during device 0's fit; 0: after it (-1 auto: only
@@ -272,6 +278,34 @@ int gpr_timing_reset(gpr_ctx_t ctx);
 int gpr_kernel(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                const double* dX, int n, const double* dXp, int m, int same, double eps,
                double* dK, int ldk);
+
+/* Out[na x nv] (ldo) = kernel(cov, hp, xa, xb) V with V nb x nv (ldv), the kernel matrix never
+ * stored: 64 x 64 tiles of it are evaluated in registers (the element code of gpr_kernel's Gram
+ * route, so every element is bit for bit the one gpr_kernel writes there) and multiplied into
+ * the result by a second FP64 MFMA.  Every description gpr_kernel accepts; `same` as there:
+ * GPR_SELF / GPR_SAME_OBJECT need na == nb and ignore dXb (GPR_SELF is the matrix gpr_fit
+ * factors).  Workspace is linear in na + nb; nothing of size na nb is allocated.  No atomics:
+ * two calls agree bit for bit (GPR_KMM_SLABS changes the summation order, nothing else).
+ * K(x, x) is evaluated in full, without a symmetry saving.  Asynchronous on the context's
+ * stream.  GPR_E_ARG, naming the argument, before anything is written: a NULL pointer, na, nb
+ * or nv < 1, ldv < nb, ldo < na, a same-object form with na != nb.  (No reference counterpart:
+ * the reference always forms the matrix.) */
+int gpr_kernel_matmul(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                      const double* dXa, int na, const double* dXb, int nb, int same, double eps,
+                      const double* dV, int nv, int ldv, double* dOut, int ldo);
+
+/* dXout[n x nrhs] (ldx) = K^{-1} B for the GPR_SELF matrix K of (cov, hp, x) by conjugate
+ * gradients from x0 = 0, every product by gpr_kernel_matmul: K is never formed and memory is
+ * O(n nrhs).  The columns are independent recurrences sharing one product per iteration; a
+ * column stops updating once ||r_c|| <= tol ||b_c||, and the call ends when all have, or after
+ * maxit iterations -- which is not an error: *iters = maxit.  relres[c] (host, nrhs) is the true
+ * residual ||b_c - K x_c|| / ||b_c|| from one more product.  Jacobi scaling by K's constant
+ * diagonal is the only preconditioning, so the iteration count grows as sqrt(cond_2(K)) <=
+ * sqrt(1 + n sigma^2 / sigma_n^2): small noise means many iterations, each a full evaluation of
+ * K.  No atomics; synchronises once per iteration (the stop test) and before returning. */
+int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                 const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
+                 double tol, int maxit, double* dXout, int ldx, int* iters, double* relres);
 
 /* a4: dK/dtheta_i (1-based i) materialised, n x n.  WN part: writes 2*sigma_n*I; a stationary
  * part: the rules above with its own W.
