@@ -329,6 +329,8 @@ struct gpr_ctx {
   DevBuf dkmm;                  // matrix-free product: slab partials (kmatmul.hip)
   DevBuf dcg;                   // conjugate gradients: r, p, K p, partial sums, scalars (cg.hip)
   int kmm_slabs = 0;            // GPR_KMM_SLABS: slabs of xb per 64 output points (0 auto)
+  DevBuf dgf;                   // matrix-free MLL gradient: [y | Z] and K^{-1} [y | Z] (kgradform.hip)
+  int kgf_slabs = 0;            // GPR_KGF_SLABS: the same for gpr_kernel_grad_form's row blocks
   int mean_free = -1;           // GPR_MEAN_FREE: gpr_predict's mean without K(x, xp) (1), with it
                                 // (0), -1 auto: matrix-free when no dwork is passed and n m > 2^29
   // upper-only K assembly for a factorisation (assembly.hip kmat_symu_kernel): its work list

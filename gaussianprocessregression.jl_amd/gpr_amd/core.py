@@ -458,6 +458,61 @@ def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAU
     return ctx.host(O) if host and out is None else O
 
 
+def kernel_grad_form(cov: AbstractKernel, hp, x, A, B, eps: float = EPS_DEFAULT,
+                     log_scale: bool = False, ctx: Optional[Context] = None) -> np.ndarray:
+    """g_j = sum_ab (A B')_ab dK_ab/dhp_j for every hyper-parameter at once, K = kernel(cov, hp, x)
+    (the matrix a fit factors) and A, B two N x r factors (or N-vectors): neither K, nor its
+    derivatives, nor the N x N weight is formed (gpr_kernel_grad_form).  Sums of SquaredExp,
+    Matern and WhiteNoise parts.  Device A, B follow kernel_matmul's layout: r x ld tensors,
+    ld >= N."""
+    ctx = ctx or default_context()
+    dx = ctx.colmajor(x)
+    n = dx.shape[0]
+    d = dx.shape[1] if dx.ndim == 2 else 1
+    kinds, nk = _kinds_arr(cov)
+    hpa, hpp = _hp_arr(hp)
+    dA, dB = ctx.colmajor(A), ctx.colmajor(B)
+    r = 1 if dA.ndim == 1 else dA.shape[0]
+    if (1 if dB.ndim == 1 else dB.shape[0]) != r:
+        raise ValueError("A and B need the same number of columns")
+    g = np.empty(len(hpa))
+    ctx.check(lib.gpr_kernel_grad_form(ctx.h, kinds, nk, hpp, d, _ptr(dx), n, _ptr(dA),
+                                       dA.shape[-1], _ptr(dB), dB.shape[-1], r, eps,
+                                       1 if log_scale else 0,
+                                       g.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+              "gpr_kernel_grad_form")
+    return g
+
+
+def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: float = 1e-6,
+                  maxit: Optional[int] = None, log_scale: bool = False,
+                  eps: float = EPS_DEFAULT):
+    """The gradient of the negative log marginal likelihood without K, K^{-1} or a factorisation
+    (gpr_mll_grad_free): one solve_cg call for [alpha | K^{-1} Z], then kernel_grad_form; the
+    trace term is Hutchinson's estimate over the probes Z (N x m; default: ``probes`` standard-
+    normal columns from the library's generator at ``seed``, 0 <= seed < 2^31).  Returns (g, iters,
+    relres)."""
+    ctx = md.ctx
+    kinds, nk = _kinds_arr(md.covar)
+    hpa, hpp = _hp_arr(md.params)
+    dZ = None if Z is None else ctx.colmajor(Z)
+    m = int(probes) if dZ is None else (1 if dZ.ndim == 1 else dZ.shape[0])
+    if dZ is not None and dZ.shape[-1] != md.n:
+        raise ValueError("Z needs N rows")
+    if not 0 <= int(seed) < 2 ** 31:
+        raise ValueError("seed must be in [0, 2^31)")
+    g = np.empty(len(hpa))
+    iters = ctypes.c_int(0)
+    relres = (ctypes.c_double * (1 + max(m, 0)))()
+    ctx.check(lib.gpr_mll_grad_free(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n,
+                                    _ptr(md.dsample()), eps, m, int(seed),
+                                    _ptr(dZ), tol, md.n if maxit is None else int(maxit),
+                                    1 if log_scale else 0,
+                                    g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                    ctypes.byref(iters), relres), "gpr_mll_grad_free")
+    return g, iters.value, np.array(relres[:])
+
+
 def kernel_grad(cov: AbstractKernel, i: int, hp, x, eps: float = EPS_DEFAULT,
                 ctx: Optional[Context] = None):
     """grad(cov, i, hp, x) (src/deriv_covar.jl:2-32): dK/dtheta_i, i is 1-based."""

@@ -243,6 +243,8 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *   GPR_KMM_SLABS      0  gpr_kernel_matmul: slabs the summed points are cut into per 64 output
  *                         points (each a workgroup; their partial products are added in slab
  *                         order); 0 auto: the fewest that give two workgroups per CU, at most 64
+ *   GPR_KGF_SLABS      0  gpr_kernel_grad_form: the same for its row blocks (the partial slots are
+ *                         added in slab order); 0 auto
  *   GPR_MEAN_FREE     -1  gpr_predict, GPR_PREDICT_MEAN: the mean by the matrix-free product (1)
  *                         or through K(x, xp) (0); -1 auto: matrix-free only when dwork is NULL
  *                         and the scratch it replaces would pass 4 GiB (n m > 2^29)
@@ -306,6 +308,36 @@ int gpr_kernel_matmul(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
 int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                  const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
                  double tol, int maxit, double* dXout, int ldx, int* iters, double* relres);
+
+/* grad[D] (HOST, hp order) = sum_ab (A B^T)_ab dK_ab/dhp_j for every hyper-parameter j at once, K
+ * the GPR_SELF matrix of (cov, hp, x) and A (n x r, lda), B (n x r, ldb) skinny device factors:
+ * neither K, nor dK/dhp_j, nor the n x n weight A B^T is formed, and the workspace is linear in
+ * n.  dK/dhp_j is gpr_kernel_grad's (dK/dsigma = (2 / |sigma|)(K_p + eps I), dK/dl_k = -2 l_k W_p
+ * (x_ak - x_bk)^2, dK/dsigma_n = 2 sigma_n I for every WhiteNoise part); log_scale: grad .*= hp,
+ * as gpr_mll_grad.  With A = B = alpha this is alpha^T dK_j alpha; with A = K^{-1} Z / m, B = Z it
+ * is Hutchinson's estimate of tr(K^{-1} dK_j) -- gpr_mll_grad_free puts the two together.
+ * Sums of SquaredExp / Matern32 / Matern52 / WhiteNoise parts, any number, any d >= 1; a Periodic
+ * part or a product marker: GPR_E_UNSUP, the message names the part, nothing is written.
+ * GPR_E_ARG, naming the argument, before anything is written: a NULL pointer, n or r < 1, lda or
+ * ldb < n.  No atomics: two calls agree bit for bit (GPR_KGF_SLABS changes the summation order,
+ * nothing else).  Synchronises.  (No reference counterpart.) */
+int gpr_kernel_grad_form(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                         const double* dX, int n, const double* dA, int lda, const double* dB,
+                         int ldb, int r, double eps, int log_scale, double* grad);
+
+/* grad[D] (HOST) ~ the gradient of the negative log marginal likelihood (gpr_mll_grad's) without
+ * K, K^{-1} or a factorisation:  -2 g_j = alpha^T dK_j alpha - tr(K^{-1} dK_j), the trace by
+ * Hutchinson's estimator (1/m) sum_c (K^{-1} z_c)^T dK_j z_c.  Probes: dZ (n x m, ld n) when not
+ * NULL, else m standard-normal columns of gpr_randn(seed, 0, ...), seed >= 0.  One gpr_solve_cg call solves
+ * K [alpha | U] = [y | Z] (tol, maxit; iters and relres[1 + m], either may be NULL, are passed
+ * through; reaching maxit is reported, not an error), then grad = -0.5 gpr_kernel_grad_form with
+ * A = [alpha | -U / m], B = [alpha | Z].  The estimate is unbiased for exact solves; its variance
+ * falls as 1 / m.  Memory O(n m).  Kernels and errors as gpr_kernel_grad_form; GPR_E_ARG also for
+ * m < 1, seed < 0, tol <= 0, maxit < 0.  Synchronises. */
+int gpr_mll_grad_free(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                      const double* dX, int n, const double* dy, double eps, int m, int seed,
+                      const double* dZ, double tol, int maxit, int log_scale, double* grad,
+                      int* iters, double* relres);
 
 /* a4: dK/dtheta_i (1-based i) materialised, n x n.  WN part: writes 2*sigma_n*I; a stationary
  * part: the rules above with its own W.
