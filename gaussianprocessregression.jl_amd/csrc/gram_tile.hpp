@@ -202,6 +202,9 @@ __device__ __forceinline__ void gram_tile(const KParams& kp, int S, const double
     }
     const double* ts = tabs + 256 * p;
     kprof_dispatch<MIX>(MIX ? kp.prof[p] : 0, [&](auto pf) {
+      // (a factor's product and the sum it goes into round separately in every caller: which of
+      // them the compiler fuses would otherwise differ from kernel to kernel)
+#pragma clang fp contract(off)
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll

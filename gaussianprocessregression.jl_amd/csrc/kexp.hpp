@@ -72,11 +72,16 @@ static __device__ __forceinline__ double kexp_s2(double dist, const double* ts) 
 // element plus one FP64 square root and two or three FMAs.  The profile is per part, i.e.
 // wave-uniform: callers branch on it once per part (kprof_dispatch), outside their element
 // loops, and the element code is compiled per profile.
+// No contraction in the Matern branch: every caller of kprof_s2 has to get the same bits (the
+// matrix-free product promises gpr_kernel's elements), and left to itself the compiler formed
+// 1 + a r as fma(a, r, 1) in one kernel and as 1 + fl(a r) in another, and may fuse the final
+// product into a caller's sum.  Each operation below rounds once, as written.
 template <int PF>
 static __device__ __forceinline__ double kprof_s2(double D, const double* ts) {
   if constexpr (PF == 0) {
     return kexp_s2(D, ts);
   } else {
+#pragma clang fp contract(off)
     const double ar = (PF == 1 ? 1.7320508075688772 : 2.23606797749979) *
                       __builtin_sqrt(D < 0.0 ? 0.0 : D);
     const double e = kexp_s2(ar, ts);

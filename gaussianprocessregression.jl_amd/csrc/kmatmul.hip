@@ -19,7 +19,10 @@
 // So K takes no pass through LDS or memory.  An element is bit for bit the one gpr_kernel's Gram
 // route writes for K(xa, xb): the operands are prepared by the same gram_prepare call (xa as the
 // assembly's rows, xb as its columns), and gram_tile forms -D from the same products (2 y_a,k)
-// y_b,k in the same k order whichever of the two operands sits on the tile's rows.
+// y_b,k in the same k order whichever of the two operands sits on the tile's rows.  (The profiles
+// round each operation on its own -- contraction is off in kprof_s2 and in gram_tile's element
+// loop -- because the compiler fused 1 + a r of the Matern profiles here and not in the assembly's
+// kernels; tests/test_gpu_kernel_matmul_bits.py compares the two bit for bit.)
 //
 // Work split.  A workgroup of 4 waves owns 64 output points and one slab of xb, which it walks in
 // 64-point blocks; wave w evaluates the tile quadrant (rows 32 (w & 1), columns 32 (w >> 1)) and

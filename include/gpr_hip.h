@@ -304,7 +304,10 @@ int gpr_kernel_matmul(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
  * residual ||b_c - K x_c|| / ||b_c|| from one more product.  Jacobi scaling by K's constant
  * diagonal is the only preconditioning, so the iteration count grows as sqrt(cond_2(K)) <=
  * sqrt(1 + n sigma^2 / sigma_n^2): small noise means many iterations, each a full evaluation of
- * K.  No atomics; synchronises once per iteration (the stop test) and before returning. */
+ * K.  No atomics: two calls agree bit for bit; synchronises once per iteration (the stop test)
+ * and before returning.  iters and relres may be NULL.  GPR_E_ARG, naming the argument, before
+ * anything is written: a NULL dX, dB or dXout, n or nrhs < 1, ldb or ldx < n, tol not positive,
+ * maxit < 0. */
 int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                  const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
                  double tol, int maxit, double* dXout, int ldx, int* iters, double* relres);

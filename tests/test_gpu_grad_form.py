@@ -52,6 +52,8 @@ CASES = [
     ("5SE+WN", 21, 63, 17, 0, 0),
     ("5SE+WN", 40, 65, 4, 0, 0),
     ("SE+M52+WN", 8, 65, 17, 0, 7),     # NaN rows between the factors' columns
+    ("SE+M52+WN", 3, 1100, 4, 0, 0),    # n > 1024: the trace's second stage, the default slabs
+    ("SE", 3, 1100, 17, 3, 0),
 ]
 
 
@@ -86,7 +88,7 @@ def _inputs(name, d, n, r, seed):
     return desc, hp, rng.random((d, n)), rng.standard_normal((n, r)), rng.standard_normal((n, r))
 
 
-def _run(desc, hp, x, A, B, pad=0):
+def _run(desc, hp, x, A, B, pad=0, log_scale=False):
     """through gpr_amd.kernel_grad_form, the factors as device buffers whose padding rows are NaN"""
     ctx = G.default_context()
     n, r = A.shape
@@ -96,7 +98,7 @@ def _run(desc, hp, x, A, B, pad=0):
         t[:, :n] = torch.from_numpy(np.ascontiguousarray(F.T)).to(ctx.device)
         dev.append(t)
     torch.cuda.synchronize()
-    return G.kernel_grad_form(PR.cov_of(desc), hp, x, dev[0], dev[1])
+    return G.kernel_grad_form(PR.cov_of(desc), hp, x, dev[0], dev[1], log_scale=log_scale)
 
 
 @pytest.mark.parametrize("name,d,n,r,slabs,pad", CASES)
@@ -117,6 +119,47 @@ def test_two_calls_agree_bit_for_bit(knobs):
     knobs("GPR_KGF_SLABS", 3)
     desc, hp, x, A, B = _inputs("SE+M52+WN", 8, 200, 17, 5)
     assert np.array_equal(_run(desc, hp, x, A, B), _run(desc, hp, x, A, B))
+
+
+@pytest.mark.parametrize("name,d,n,r", [("SE+M52+WN", 1, 64, 70), ("SE", 8, 63, 17),
+                                        ("5SE+WN", 21, 63, 17)], ids=["S=1", "S=2", "run-time S"])
+def test_log_scale_is_one_multiplication_by_hp(name, d, n, r):
+    """log_scale: grad .*= hp on the host after the form, so the result is the plain call's (two
+    calls agree bit for bit) times hp[i], rounded once"""
+    desc, hp, x, A, B = _inputs(name, d, n, r, 1000 * n + 10 * r + d)
+    g = _run(desc, hp, x, A, B)
+    gl = _run(desc, hp, x, A, B, log_scale=True)
+    assert np.all(np.isfinite(g)) and np.all(g != 0.0)
+    assert np.array_equal(gl, g * hp)
+
+
+# (what changes, the word the message must carry)
+BAD_ARGS = [(dict(dX=None), "dX is"), (dict(dA=None), "dA is"), (dict(dB=None), "dB is"),
+            (dict(grad=None), "grad is"), (dict(n=0), "n="), (dict(r=0), "r="),
+            (dict(lda=-1), "lda"), (dict(ldb=-1), "ldb")]
+
+
+@pytest.mark.parametrize("change,word", BAD_ARGS, ids=[f"{list(c)[0]}={list(c.values())[0]}" for c, _ in BAD_ARGS])
+def test_argument_errors(change, word):
+    """GPR_E_ARG naming the argument, before anything is written"""
+    from gpr_amd import _lib as L, core
+    ctx = G.default_context()
+    desc, hp, x, A, B = _inputs("SE+M52+WN", 3, 70, 4, 9)
+    d, n = x.shape
+    kinds, nk = core._kinds_arr(PR.cov_of(desc))
+    g = np.full(len(hp), -7.5)
+    a = dict(dX=ctx.colmajor(x), n=n, dA=ctx.colmajor(A), lda=n, dB=ctx.colmajor(B), ldb=n, r=4,
+             grad=g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    a.update(change)
+    for k in ("lda", "ldb"):  # -1: one short of n
+        a[k] = n - 1 if a[k] == -1 else a[k]
+    rc = L.lib.gpr_kernel_grad_form(ctx.h, kinds, nk, core._hp_arr(hp)[1], d, core._ptr(a["dX"]),
+                                    a["n"], core._ptr(a["dA"]), a["lda"], core._ptr(a["dB"]),
+                                    a["ldb"], a["r"], R.EPS, 0, a["grad"])
+    msg = L.lib.gpr_last_error(ctx.h).decode()
+    assert rc == -1, (rc, msg)  # GPR_E_ARG
+    assert word in msg, msg
+    assert np.all(g == -7.5)
 
 
 @pytest.mark.parametrize("desc", [[PER], [[SE, PER], WN]], ids=["PER", "SE*PER+WN"])

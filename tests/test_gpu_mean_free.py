@@ -57,6 +57,15 @@ def test_same_object_rule(knobs):
     np.testing.assert_allclose(free, K5 @ alpha, **TOL)
 
 
+def test_predict_mean_from_several_columns():
+    """an N x 3 alpha: mu = K(xp, x) alpha column by column, against the long-double kernel"""
+    desc, hp, x, y, xp, md = _model("M52+PER+WN", 300, 257)
+    alpha = np.random.default_rng(3).standard_normal((300, 3))
+    mu = G.predict_mean_from(md, alpha, xp)
+    assert mu.shape == (257, 3)
+    np.testing.assert_allclose(mu, R.kernel_ld(desc, hp, xp, x).astype(np.float64) @ alpha, **TOL)
+
+
 def test_predict_mean_from_given_weights(knobs):
     desc, hp, x, y, xp, md = _model("M52+PER+WN", 300, 257)
     knobs("GPR_MEAN_FREE", 0)
