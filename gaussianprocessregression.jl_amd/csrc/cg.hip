@@ -23,8 +23,18 @@
 // Limits.  Memory is O(n nrhs): r, p, q (3 n nrhs doubles) beside the product's linear
 // workspace.  The iteration count is governed by sqrt(cond_2(K)) -- about 0.5 sqrt(cond) ln(2 /
 // tol) -- and cond_2 <= 1 + n sigma^2 / sigma_n^2: small noise means many iterations, each a full
-// evaluation of K.  A low-rank preconditioner is the remedy and is not part of this file.
-// Reaching maxit is not an error.
+// evaluation of K.  Reaching maxit is not an error.
+//
+// The remedy is a low-rank preconditioner: with rank > 0 (gpr_solve_pcg, or the knob GPR_CG_PRECOND
+// for gpr_solve_cg) z = P^{-1} r with P = L L^T + delta I from a pivoted Cholesky factor of the
+// noise-free kernel (pchol.hip), and the recurrence becomes
+//   rho = r.z,  alpha = rho / p.q,  x += alpha p,  r -= alpha q,  z = P^{-1} r,
+//   beta = rho_new / rho,  p = z + beta p.
+// cg_dot_kernel and cg_step_xr_kernel serve unchanged (the slot's first scalar holds rho, the Jacobi
+// factor is 1); pchol_apply leaves z and the block partials of r.z; pcg_step_p_kernel sums both
+// r.z and r.r, forms beta and p and writes the next slot.  The stop test stays on r.r, the freezing
+// and the two slots are the same.  With rank 0 none of this runs: the kernels above, in the order
+// above.
 #include <algorithm>
 #include <cmath>
 
@@ -156,6 +166,60 @@ __global__ __launch_bounds__(256) void cg_step_p_kernel(
   }
 }
 
+// sum of up to PCH_MAXB = 4 x 256 partials: each thread four in order, then the fixed tree
+__device__ __forceinline__ double pcg_sum_rz(const double* __restrict__ rz, int nz, double* red) {
+  double v = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    const int b = 4 * (int)threadIdx.x + k;
+    if (b < nz) v += rz[b];
+  }
+  return cg_block_sum(v, red);
+}
+
+// grid (nblk, nrhs).  p = z; block 0: the slot's r.r becomes rho = r.z (the frozen flag stays)
+__global__ __launch_bounds__(256) void pcg_start_kernel(const double* __restrict__ rz, int nz,
+                                                        int nrhs, double* __restrict__ sc, int n,
+                                                        const double* __restrict__ Z,
+                                                        double* __restrict__ P) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const double rho = pcg_sum_rz(rz + (size_t)c * PCH_MAXB, nz, red);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    P[(size_t)c * n + i] = Z[(size_t)c * n + i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) cg_slot(sc, 0, nrhs, c)[0] = rho;
+}
+
+// grid (nblk, nrhs).  beta = r.z / previous r.z; p = z + beta p; block 0 fills the other slot: the
+// new r.z and frozen = r.r <= tol^2 b.b.  A frozen column carries its slot over.
+__global__ __launch_bounds__(256) void pcg_step_p_kernel(
+    const double* __restrict__ rr, int nblk, const double* __restrict__ rz, int nz, int nrhs,
+    int slot, double* __restrict__ sc, const double* __restrict__ bb, double tol2, int n,
+    const double* __restrict__ Z, double* __restrict__ P) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  const double* cur = cg_slot(sc, slot, nrhs, c);
+  double* nxt = cg_slot(sc, slot ^ 1, nrhs, c);
+  if (cur[1] != 0.0) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      nxt[0] = cur[0];
+      nxt[1] = 1.0;
+    }
+    return;
+  }
+  const double num =
+      cg_block_sum((int)threadIdx.x < nblk ? rr[(size_t)c * CG_MAXB + threadIdx.x] : 0.0, red);
+  const double rho = pcg_sum_rz(rz + (size_t)c * PCH_MAXB, nz, red);
+  const double beta = rho / cur[0];
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const size_t k = (size_t)c * n + i;
+    P[k] = fma(beta, P[k], Z[k]);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    nxt[0] = rho;
+    nxt[1] = num <= tol2 * bb[c] ? 1.0 : 0.0;
+  }
+}
+
 // grid (nblk, nrhs).  part[c][blk] = partial ||b - q||^2
 __global__ __launch_bounds__(256) void cg_resid_kernel(const double* __restrict__ B, size_t ldb,
                                                        const double* __restrict__ Q, int n,
@@ -202,13 +266,12 @@ struct PinnedDoubles {  // the stop test's host copy
   }
 };
 
-}  // namespace
-
-extern "C" {
-
-int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
-                 const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
-                 double tol, int maxit, double* dXout, int ldx, int* iters, double* relres) {
+// the solve: rank 0 is the plain recurrence, rank > 0 the preconditioned one (rank_out: the rank
+// the factor reached)
+int cg_solve(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d, const double* dX,
+             int n, const double* dB, int nrhs, int ldb, double eps, double tol, int maxit,
+             int rank, double rtol, double* dXout, int ldx, int* iters, double* relres,
+             int* rank_out) {
   KParams kp;
   GPR_TRY(make_kparams(ctx, kinds, nk, hp, d, eps, &kp, nullptr));
   if (!dX) return set_err(ctx, GPR_E_ARG, "dX is NULL");
@@ -220,15 +283,27 @@ int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   if (ldx < n) return set_err(ctx, GPR_E_ARG, "ldx=%d < n=%d", ldx, n);
   if (!(tol > 0.0)) return set_err(ctx, GPR_E_ARG, "tol=%g is not positive", tol);
   if (maxit < 0) return set_err(ctx, GPR_E_ARG, "maxit=%d < 0", maxit);
-  const double dinv = 1.0 / cg_diagonal(kp), tol2 = tol * tol;
+  if (rank < 0 || rank > 256)
+    return set_err(ctx, GPR_E_ARG, "rank=%d outside [0, 256]", rank);
+  if (!(rtol >= 0.0)) return set_err(ctx, GPR_E_ARG, "rtol=%g is negative", rtol);
+  rank = std::min(rank, n);
+  const bool pre = rank > 0;
+  const double dinv = pre ? 1.0 : 1.0 / cg_diagonal(kp), tol2 = tol * tol;
   const size_t nn = (size_t)n * nrhs, np = (size_t)nrhs * CG_MAXB;
   // r | p | q | p.q partials | r.r partials | two scalar slots | b.b | the final residuals
-  GPR_TRY(ensure_buf(ctx, ctx->dcg, 3 * nn + 2 * np + 6 * (size_t)nrhs));
+  // (| z | r.z partials, preconditioned)
+  GPR_TRY(ensure_buf(ctx, ctx->dcg, 3 * nn + 2 * np + 6 * (size_t)nrhs +
+                                        (pre ? nn + (size_t)nrhs * PCH_MAXB : 0)));
   double* R = ctx->dcg;
   double *P = R + nn, *Q = P + nn, *pq = Q + nn, *rr = pq + np, *sc = rr + np;
   double *bb = sc + 4 * (size_t)nrhs, *res = bb + nrhs;
+  double *Z = res + nrhs, *rz = Z + nn;
   PinnedDoubles host;
   HIP_TRY(ctx, hipHostMalloc((void**)&host.p, sizeof(double) * 2 * nrhs, hipHostMallocDefault));
+  PcholOps pc{};
+  if (pre) GPR_TRY(pchol_prepare(ctx, kp, dX, n, rank, rtol, nrhs, &pc));
+  if (rank_out) *rank_out = pre ? pc.k : 0;
+  int nz = 0;
   KmmOps ops;
   GPR_TRY(kmm_prepare(ctx, kp, dX, n, nullptr, n, GPR_SELF, &ops));
   const int nblk = std::max(1, std::min(CG_MAXB, (n + 1023) / 1024));
@@ -236,6 +311,10 @@ int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
   hipStream_t st = ctx->stream;
   cg_init_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, n, dinv, dXout, (size_t)ldx, R, P, rr);
   cg_init_scalars_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, nrhs, tol2, sc, bb);
+  if (pre) {
+    GPR_TRY(pchol_apply(ctx, pc, R, nrhs, Z, rz, &nz));
+    pcg_start_kernel<<<grid, 256, 0, st>>>(rz, nz, nrhs, sc, n, Z, P);
+  }
   LAUNCH_CHECK(ctx);
   // the stop test reads the slot's (r.r, frozen) pairs: every column frozen
   auto all_frozen = [&](int slot, bool* done) {
@@ -256,7 +335,12 @@ int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
     cg_dot_kernel<<<grid, 256, 0, st>>>(P, Q, n, pq);
     cg_step_xr_kernel<<<grid, 256, 0, st>>>(pq, nblk, nrhs, slot, sc, dinv, n, P, Q, dXout,
                                             (size_t)ldx, R, rr);
-    cg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, nrhs, slot, sc, bb, tol2, dinv, n, R, P);
+    if (pre) {
+      GPR_TRY(pchol_apply(ctx, pc, R, nrhs, Z, rz, &nz));
+      pcg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, rz, nz, nrhs, slot, sc, bb, tol2, n, Z, P);
+    } else {
+      cg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, nrhs, slot, sc, bb, tol2, dinv, n, R, P);
+    }
     LAUNCH_CHECK(ctx);
     ++it;
     GPR_TRY(all_frozen(it & 1, &done));
@@ -274,6 +358,25 @@ int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int 
       relres[c] = host.p[c] > 0.0 ? std::sqrt(host.p[nrhs + c] / host.p[c]) : 0.0;
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                 const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
+                 double tol, int maxit, double* dXout, int ldx, int* iters, double* relres) {
+  return cg_solve(ctx, kinds, nk, hp, d, dX, n, dB, nrhs, ldb, eps, tol, maxit,
+                  ctx ? ctx->cg_precond : 0, 0.0, dXout, ldx, iters, relres, nullptr);
+}
+
+int gpr_solve_pcg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                  const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
+                  double tol, int maxit, int rank, double rtol, double* dXout, int ldx, int* iters,
+                  double* relres, int* rank_out) {
+  return cg_solve(ctx, kinds, nk, hp, d, dX, n, dB, nrhs, ldb, eps, tol, maxit, rank, rtol, dXout,
+                  ldx, iters, relres, rank_out);
 }
 
 }  // extern "C"

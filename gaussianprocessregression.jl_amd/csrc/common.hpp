@@ -329,6 +329,11 @@ struct gpr_ctx {
   DevBuf dkmm;                  // matrix-free product: slab partials (kmatmul.hip)
   DevBuf dcg;                   // conjugate gradients: r, p, K p, partial sums, scalars (cg.hip)
   int kmm_slabs = 0;            // GPR_KMM_SLABS: slabs of xb per 64 output points (0 auto)
+  // the pivoted-Cholesky preconditioner (pchol.hip): the build's state (residual diagonal, pivot
+  // partials, pivots, flag) | the solve's factor L, C = delta I + L^T L and t | the slab partials
+  // of L^T R | a Periodic part's unit features
+  DevBuf dpch, dpchl, dpchw, dpchcs;
+  int cg_precond = 0;           // GPR_CG_PRECOND: the preconditioner rank gpr_solve_cg uses (0: none)
   DevBuf dgf;                   // matrix-free MLL gradient: [y | Z] and K^{-1} [y | Z] (kgradform.hip)
   int kgf_slabs = 0;            // GPR_KGF_SLABS: the same for gpr_kernel_grad_form's row blocks
   int mean_free = -1;           // GPR_MEAN_FREE: gpr_predict's mean without K(x, xp) (1), with it
@@ -512,6 +517,26 @@ int kmm_prepare(gpr_ctx* ctx, const KParams& kp, const double* dXa, int na, cons
                 int nb, int same, KmmOps* o);
 int kmm_apply(gpr_ctx* ctx, const KmmOps& o, const double* dV, int nv, int ldv, double* dOut,
               int ldo);
+// pchol.hip: the rank-k partial pivoted Cholesky L (n x k, ldl) of the noise-free cross-form kernel
+// K_c of (kp, x), one launch per step; piv (host, may be null) gets the 0-based pivots and
+// *rank_out the rank reached (< rank when the largest residual diagonal fell to rtol n c)
+int pchol_factor(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, int rank, double rtol,
+                 double* dL, int ldl, int* piv, int* rank_out);
+// the preconditioner P = L L^T + delta I of the GPR_SELF matrix, ready to apply to up to nrhs
+// columns: L in ctx->dpchl, then C = delta I + L^T L and its factor.  Synchronises.
+constexpr int PCH_MAXB = 1024;  // most r.z partials per column
+struct PcholOps {
+  const double* L;  // n x k, ld n
+  int n, k, nrhs;   // k: the rank reached
+  double delta;
+  const double* U;  // C's upper factor (k x k, ld k)
+  double* T;        // k x nrhs, ld k
+};
+int pchol_prepare(gpr_ctx* ctx, const KParams& kp, const double* dX, int n, int rank, double rtol,
+                  int nrhs, PcholOps* o);
+// Z (n x nrhs, ld n) = P^{-1} R (ld n); rz[c * PCH_MAXB + b], b < *nblk: block partials of r_c.z_c
+int pchol_apply(gpr_ctx* ctx, const PcholOps& o, const double* R, int nrhs, double* Z, double* rz,
+                int* nblk);
 // ctx->dxs <- per part and point [cos(2 pi x_k / p_k) | sin(2 pi x_k / p_k)] (2d wide, without
 // l_k) for the Periodic parts of kp (the other parts' rows are not for use); the MLL gradient's
 // per-point table

@@ -311,6 +311,7 @@ const Knob kKnobs[] = {
     {"GPR_KMM_SLABS", &gpr_ctx::kmm_slabs, nullptr},
     {"GPR_KGF_SLABS", &gpr_ctx::kgf_slabs, nullptr},
     {"GPR_MEAN_FREE", &gpr_ctx::mean_free, nullptr},
+    {"GPR_CG_PRECOND", &gpr_ctx::cg_precond, nullptr},
 };
 
 void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
@@ -322,6 +323,7 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
     if (k.ip == &gpr_ctx::cv_streams) iv = std::max(1, std::min(iv, (int)gpr_ctx::CV_MAX_SUB));
     if (k.ip == &gpr_ctx::pgrad_slab) iv = (std::max(iv, 64) + 63) / 64 * 64;
     if (k.ip == &gpr_ctx::kmm_slabs || k.ip == &gpr_ctx::kgf_slabs) iv = std::max(0, iv);
+    if (k.ip == &gpr_ctx::cg_precond) iv = std::max(0, std::min(iv, 256));
     ctx->*k.ip = iv;
   } else {
     ctx->*k.dp = v;
@@ -335,7 +337,7 @@ DevBuf gpr_ctx::*const kWorkspaces[] = {
     &gpr_ctx::dxps,   &gpr_ctx::dscr_wt,  &gpr_ctx::dpanel_rhs, &gpr_ctx::dgA,   &gpr_ctx::dgB,
     &gpr_ctx::dgc,    &gpr_ctx::dpadA,    &gpr_ctx::dpadB,      &gpr_ctx::dagb,  &gpr_ctx::deig,
     &gpr_ctx::ddc,    &gpr_ctx::dtri,     &gpr_ctx::dkmm,       &gpr_ctx::dcg,
-    &gpr_ctx::dgf,
+    &gpr_ctx::dgf,    &gpr_ctx::dpch,     &gpr_ctx::dpchl,      &gpr_ctx::dpchw, &gpr_ctx::dpchcs,
 };
 
 const Knob* knob_find(const char* name) {

@@ -70,6 +70,9 @@ _SIGS = {
     "gpr_kernel": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _d, _p, _i]),
     "gpr_kernel_matmul": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i]),
     "gpr_solve_cg": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _d, _d, _i, _p, _i, _ip, _dp]),
+    "gpr_pchol": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _d, _i, _d, _p, _i, _ip, _ip]),
+    "gpr_solve_pcg": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _i, _d, _d, _i, _i, _d, _p, _i, _ip,
+                           _dp, _ip]),
     "gpr_kernel_grad_form": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _i, _d, _i, _dp]),
     "gpr_mll_grad_free": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _d, _i, _i, _p, _d, _i, _i, _dp,
                                _ip, _dp]),

@@ -458,6 +458,27 @@ def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAU
     return ctx.host(O) if host and out is None else O
 
 
+def pivoted_cholesky(cov: AbstractKernel, hp, x, rank: int, rtol: float = 0.0,
+                     eps: float = EPS_DEFAULT, ctx: Optional[Context] = None):
+    """The rank-``rank`` partial pivoted Cholesky factor of the noise-free kernel of (cov, hp, x)
+    (gpr_pchol): (L, piv) with L N x r and piv the r 0-based pivots, r <= rank the rank reached
+    (smaller when the largest residual diagonal fell to rtol N c).  L L^T + (sigma_n^2 + eps per
+    term) I is solve_cg's preconditioner."""
+    ctx = ctx or default_context()
+    dx = ctx.colmajor(x)
+    n = dx.shape[0]
+    d = dx.shape[1] if dx.ndim == 2 else 1
+    kinds, nk = _kinds_arr(cov)
+    hpa, hpp = _hp_arr(hp)
+    rank = int(rank)
+    L = ctx.empty(max(rank, 1), n)
+    piv = (ctypes.c_int * max(rank, 1))()
+    r = ctypes.c_int(0)
+    ctx.check(lib.gpr_pchol(ctx.h, kinds, nk, hpp, d, _ptr(dx), n, eps, rank, float(rtol), _ptr(L),
+                            n, piv, ctypes.byref(r)), "gpr_pchol")
+    return ctx.host(L[:r.value]), np.array(piv[:r.value], dtype=np.int64)
+
+
 def kernel_grad_form(cov: AbstractKernel, hp, x, A, B, eps: float = EPS_DEFAULT,
                      log_scale: bool = False, ctx: Optional[Context] = None) -> np.ndarray:
     """g_j = sum_ab (A B')_ab dK_ab/dhp_j for every hyper-parameter at once, K = kernel(cov, hp, x)
@@ -486,12 +507,13 @@ def kernel_grad_form(cov: AbstractKernel, hp, x, A, B, eps: float = EPS_DEFAULT,
 
 def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: float = 1e-6,
                   maxit: Optional[int] = None, log_scale: bool = False,
-                  eps: float = EPS_DEFAULT):
+                  eps: float = EPS_DEFAULT, precond_rank: int = 0):
     """The gradient of the negative log marginal likelihood without K, K^{-1} or a factorisation
     (gpr_mll_grad_free): one solve_cg call for [alpha | K^{-1} Z], then kernel_grad_form; the
     trace term is Hutchinson's estimate over the probes Z (N x m; default: ``probes`` standard-
-    normal columns from the library's generator at ``seed``, 0 <= seed < 2^31).  Returns (g, iters,
-    relres)."""
+    normal columns from the library's generator at ``seed``, 0 <= seed < 2^31).  ``precond_rank``:
+    the rank of the solve's pivoted-Cholesky preconditioner (the knob GPR_CG_PRECOND, set for this
+    call and restored).  Returns (g, iters, relres)."""
     ctx = md.ctx
     kinds, nk = _kinds_arr(md.covar)
     hpa, hpp = _hp_arr(md.params)
@@ -504,12 +526,17 @@ def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: fl
     g = np.empty(len(hpa))
     iters = ctypes.c_int(0)
     relres = (ctypes.c_double * (1 + max(m, 0)))()
-    ctx.check(lib.gpr_mll_grad_free(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n,
-                                    _ptr(md.dsample()), eps, m, int(seed),
-                                    _ptr(dZ), tol, md.n if maxit is None else int(maxit),
-                                    1 if log_scale else 0,
-                                    g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                    ctypes.byref(iters), relres), "gpr_mll_grad_free")
+    knob = ctx.get_knob("GPR_CG_PRECOND")
+    ctx.set_knob("GPR_CG_PRECOND", int(precond_rank))
+    try:
+        ctx.check(lib.gpr_mll_grad_free(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n,
+                                        _ptr(md.dsample()), eps, m, int(seed),
+                                        _ptr(dZ), tol, md.n if maxit is None else int(maxit),
+                                        1 if log_scale else 0,
+                                        g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                        ctypes.byref(iters), relres), "gpr_mll_grad_free")
+    finally:
+        ctx.set_knob("GPR_CG_PRECOND", knob)
     return g, iters.value, np.array(relres[:])
 
 
@@ -931,11 +958,14 @@ def predict_mean_from(md: GPRModel, alpha, xp, eps: float = EPS_DEFAULT) -> np.n
 
 
 def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = None,
-             eps: float = EPS_DEFAULT):
+             eps: float = EPS_DEFAULT, precond_rank: int = 0, precond_rtol: float = 0.0):
     """K^{-1} B by conjugate gradients on the matrix a fit factors, every product matrix-free
     (gpr_solve_cg): memory O(N), no preconditioner beyond K's constant diagonal, iterations ~
     sqrt(cond(K)).  B defaults to md.y; maxit to N.  Returns (alpha, iters, relres) with relres
-    the true ||b - K alpha|| / ||b|| per column; reaching maxit is reported, not raised."""
+    the true ||b - K alpha|| / ||b|| per column; reaching maxit is reported, not raised.
+    ``precond_rank`` > 0 (at most 256): the pivoted-Cholesky preconditioner of that rank
+    (gpr_solve_pcg, ``precond_rtol`` its early stop), which cuts the iterations at small sigma_n; 0
+    is the plain call."""
     ctx = md.ctx
     kinds, nk = _kinds_arr(md.covar)
     hpa, hpp = _hp_arr(md.params)
@@ -944,9 +974,16 @@ def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = Non
     X = ctx.empty(md.n) if dB.ndim == 1 else ctx.empty(nrhs, md.n)
     iters = ctypes.c_int(0)
     relres = (ctypes.c_double * nrhs)()
-    ctx.check(lib.gpr_solve_cg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB), nrhs,
-                               dB.shape[-1], eps, tol, md.n if maxit is None else int(maxit),
-                               _ptr(X), md.n, ctypes.byref(iters), relres), "gpr_solve_cg")
+    maxit = md.n if maxit is None else int(maxit)
+    if precond_rank:
+        ctx.check(lib.gpr_solve_pcg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB), nrhs,
+                                    dB.shape[-1], eps, tol, maxit, int(precond_rank),
+                                    float(precond_rtol), _ptr(X), md.n, ctypes.byref(iters), relres,
+                                    None), "gpr_solve_pcg")
+    else:
+        ctx.check(lib.gpr_solve_cg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB), nrhs,
+                                   dB.shape[-1], eps, tol, maxit,
+                                   _ptr(X), md.n, ctypes.byref(iters), relres), "gpr_solve_cg")
     return ctx.host(X), iters.value, np.array(relres[:])
 
 

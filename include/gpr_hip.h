@@ -248,6 +248,9 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *   GPR_MEAN_FREE     -1  gpr_predict, GPR_PREDICT_MEAN: the mean by the matrix-free product (1)
  *                         or through K(x, xp) (0); -1 auto: matrix-free only when dwork is NULL
  *                         and the scratch it replaces would pass 4 GiB (n m > 2^29)
+ *   GPR_CG_PRECOND     0  gpr_solve_cg (and with it gpr_mll_grad_free): the rank of the pivoted-
+ *                         Cholesky preconditioner (gpr_solve_pcg's rank, rtol 0; at most 256);
+ *                         0: none -- the plain recurrence, bit for bit
  * A gpr_mgpu handle has knobs of its own, read from the environment once at gpr_mgpu_create
  * and changed with gpr_mgpu_set_knob / gpr_mgpu_get_knob (below):
  *   GPR_MGPU_STREAM   -1  1: stream U out during device 0's fit; 0: after it (-1 auto: only
@@ -311,6 +314,35 @@ int gpr_kernel_matmul(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
 int gpr_solve_cg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
                  const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
                  double tol, int maxit, double* dXout, int ldx, int* iters, double* relres);
+
+/* The rank-k partial pivoted Cholesky factor L (n x rank, ldl, column-major, device) of the
+ * noise-free kernel K_c of (cov, hp, x): the cross form -- no eps, no noise -- whose diagonal is the
+ * constant c = sum over terms of the factors' sigma^2 product.  Step m takes the point with the
+ * largest residual diagonal d_i (ties: the lower index) as pivot and writes column m,
+ * L[a, m] = (K_c(x_a, x_i) - sum_{j<m} L[a, j] L[i, j]) / sqrt(d_i); it stops early, with
+ * *rank_out = m, once d_i <= rtol n c (rtol = 0: only at d_i <= 0).  Columns >= *rank_out are not
+ * written.  piv (HOST, rank ints) gets the 0-based pivots, *rank_out the rank reached.  One launch
+ * per step, all enqueued at once; no atomics: two calls agree bit for bit.  Every description
+ * gpr_kernel_matmul accepts (eps enters only gpr_solve_pcg's delta).  Synchronises.  GPR_E_ARG,
+ * naming the argument, before anything is written: a NULL pointer, n < 1, rank < 1 or > min(n,
+ * 256), ldl < n, rtol < 0. */
+int gpr_pchol(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d, const double* dX,
+              int n, double eps, int rank, double rtol, double* dL, int ldl, int* piv,
+              int* rank_out);
+
+/* gpr_solve_cg preconditioned by P = L L^T + delta I, L = gpr_pchol(rank, rtol) and delta =
+ * sigma_n^2 + eps (number of terms), so that K = K_c + delta I: z = P^{-1} r = (r - L C^{-1} L^T r)
+ * / delta with C = delta I + L^T L factored once (gpr_potrf_upper) and the two skinny products on
+ * FP64 MFMA.  The products K p stay the exact matrix-free ones and the stop test stays ||r_c|| <=
+ * tol ||b_c||, so the result is gpr_solve_cg's up to the iteration's rounding, in fewer iterations
+ * the smaller sigma_n is.  rank = 0 IS gpr_solve_cg, bit for bit; rank > min(n, 256) is clamped
+ * to n and refused above 256.  *rank_out (may be NULL): the rank the factor reached.  Extra memory
+ * n rank + rank^2 + the products' slab partials.  GPR_E_ARG as gpr_solve_cg, and for rank < 0 or
+ * > 256, rtol < 0, or delta = 0. */
+int gpr_solve_pcg(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                  const double* dX, int n, const double* dB, int nrhs, int ldb, double eps,
+                  double tol, int maxit, int rank, double rtol, double* dXout, int ldx, int* iters,
+                  double* relres, int* rank_out);
 
 /* grad[D] (HOST, hp order) = sum_ab (A B^T)_ab dK_ab/dhp_j for every hyper-parameter j at once, K
  * the GPR_SELF matrix of (cov, hp, x) and A (n x r, lda), B (n x r, ldb) skinny device factors:
