@@ -329,6 +329,8 @@ struct gpr_ctx {
   DevBuf dkmm;                  // matrix-free product: slab partials (kmatmul.hip)
   DevBuf dcg;                   // conjugate gradients: r, p, K p, partial sums, scalars (cg.hip)
   int kmm_slabs = 0;            // GPR_KMM_SLABS: slabs of xb per 64 output points (0 auto)
+  int kmm_sym = 0;              // GPR_KMM_SYM: same-points passes of <= 16 columns evaluate only the
+                                // tiles I <= J of K(x, x) (kmatmul_sym_kernel); 0: every tile
   // the pivoted-Cholesky preconditioner (pchol.hip): the build's state (residual diagonal, pivot
   // partials, pivots, flag) | the solve's factor L, C = delta I + L^T L and t | the slab partials
   // of L^T R | a Periodic part's unit features

@@ -309,6 +309,7 @@ const Knob kKnobs[] = {
     {"GPR_APPEND_SWEEP", &gpr_ctx::append_sweep, nullptr},
     {"GPR_REMOVE_SWEEP", &gpr_ctx::remove_sweep, nullptr},
     {"GPR_KMM_SLABS", &gpr_ctx::kmm_slabs, nullptr},
+    {"GPR_KMM_SYM", &gpr_ctx::kmm_sym, nullptr},
     {"GPR_KGF_SLABS", &gpr_ctx::kgf_slabs, nullptr},
     {"GPR_MEAN_FREE", &gpr_ctx::mean_free, nullptr},
     {"GPR_CG_PRECOND", &gpr_ctx::cg_precond, nullptr},
@@ -324,6 +325,7 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
     if (k.ip == &gpr_ctx::pgrad_slab) iv = (std::max(iv, 64) + 63) / 64 * 64;
     if (k.ip == &gpr_ctx::kmm_slabs || k.ip == &gpr_ctx::kgf_slabs) iv = std::max(0, iv);
     if (k.ip == &gpr_ctx::cg_precond) iv = std::max(0, std::min(iv, 256));
+    if (k.ip == &gpr_ctx::kmm_sym) iv = iv != 0;
     ctx->*k.ip = iv;
   } else {
     ctx->*k.dp = v;

@@ -45,8 +45,8 @@
 // (ctx->dkmm, only when S > 1, and S <= 64 falls to 1 as na grows) -- linear in na + nb; nothing
 // on this path is sized by na nb.
 //
-// Not done here: K(x, x) is evaluated in full (one tile serving both triangles needs the tile in
-// the transposed layout as well).
+// kmatmul_kernel evaluates K(x, x) in full; kmatmul_sym_kernel (below, GPR_KMM_SYM) evaluates the
+// tiles on and above the diagonal and transposes each in registers for the other triangle.
 #include <algorithm>
 #include <cstdint>
 
@@ -261,6 +261,268 @@ int kmm_launch_nv(gpr_ctx* ctx, const KmmOps& o, const KParams& g, int p0, const
                    : kmm_launch<SC, 4>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum);
 }
 
+// ---- the symmetric route: K(x, x) V from the tiles I <= J alone (GPR_KMM_SYM) -------------------
+// A tile T (rows: block J, columns: block I) serves Out[I] += T^T V[J] as above and, transposed,
+// Out[J] += T V[I].  The second product sums over the tile's columns, and both MFMA operand
+// layouts carry the summed index on l >> 4, the tile's row axis: it needs T^T in the tile's own
+// register layout.  Four MFMAs per 16 x 16 block against a constant give exactly that: register q
+// taken as the A operand is A[m = l & 15][k = l >> 4] = T[4 q + k][m]; with B_q[k][n] =
+// (n == 4 q + k) the four products sum to D[m][n] = T[n][m], and D's register layout
+// (m = 4 q' + (l >> 4), n = l & 15) is the tile's.  Products by 1.0 and sums with zeros: exact.
+// Block (rb, cb) of a wave's quadrant is block (cb, rb) of the transposed quadrant, so nothing
+// leaves the wave (no LDS, no barrier).
+//
+// Work split.  A workgroup owns a band of G consecutive blocks I (kmm_sym_g: 4, 2 or 1) and one slab of the band's walk
+// over J >= the band's first block.  V of the band's blocks is staged in LDS once, V[J] per step
+// with the register prefetch above.  Per J it evaluates the band's tiles with I <= J (the tile
+// I == J by the DIAG instance, direct product only: it is whole and symmetric in itself), each into
+// the persistent Out[I] accumulators (8 registers per block of the band) and, transposed, into one
+// Out[J] accumulator, which the two waves that share those rows add through LDS (wc = 0 plus
+// wc = 1) and store once per J: one 64 x 16 flush per G tiles, n^2 nv / (64 G) doubles in all
+// each way.  The grid is (slabs, bands of this launch); nobody waits on another workgroup.  Walks
+// shorten as the band index grows: bands launch in index order, the longest first.
+// Workspace (ctx->dkmm, linear in n): at most KMS_P bands per launch, each with one n x nvc
+// partial of Out[J] (its slabs write disjoint rows of it) and one (64 G) x nvc partial of Out[I]
+// per slab; kmm_sym_reduce_kernel adds them in band, then slab order, and the next launch's
+// bands reuse the space in stream order.  No atomics: two calls agree bit for bit.
+// blocks per band: the most whose accumulators the instance's registers hold without scratch,
+// two workgroups per CU (256 registers a lane) as kmatmul_kernel
+template <int SC, bool MIX, bool PROD>
+constexpr int kmm_sym_g() { return SC == 0 ? 1 : (MIX || PROD ? 2 : 4); }
+constexpr int KMS_P = 64;  // most bands of one launch
+
+template <int SC, bool MIX, bool PROD, int G>
+__global__ __launch_bounds__(256, 2) void kmatmul_sym_kernel(
+    KParams kp, int Srt, const double* __restrict__ gR, const double* __restrict__ gC,
+    const double* __restrict__ nrm, int nblk16, int n, int band0, int nslab,
+    const double* __restrict__ V, size_t ldv, int nvc, int vec, double* __restrict__ Wt,
+    double* __restrict__ Wd) {
+  extern __shared__ double dyn_lds[];
+  double* Vs = dyn_lds;                  // V[J]: 16 columns x KMM_VS
+  double* Vb = Vs + 16 * KMM_VS;         // V of the band: G x 16 x KMM_VS
+  double* red = Vb + G * 16 * KMM_VS;    // Out[J] hand-over: 2 row halves x 8 x 64
+  double* tabs = red + 1024;             // nse exp tables
+  double* tmw = tabs + 256 * kp.nse;     // PROD: the running products (16 x 256)
+  const int S = SC > 0 ? SC : Srt;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wr = w & 1, wc = w >> 1;
+  const int nblk = (n + KT - 1) / KT;
+  const int ib0 = (band0 + (int)blockIdx.y) * G;  // < nblk
+  const int sb = (nblk - ib0 + nslab - 1) / nslab;
+  const int jb_lo = ib0 + blockIdx.x * sb;
+  const int jb_hi = min(jb_lo + sb, nblk);  // (an empty slab writes zeros)
+  load_part_tables(kp, tabs);
+  kv2 vr[2];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    kmm_fetch_v<1>(V, ldv, n, nvc, (ib0 + g) * KT, vec, vr);
+    kmm_stage_v<1>(vr, Vb + g * 16 * KMM_VS);
+  }
+  kmm_fetch_v<1>(V, ldv, n, nvc, jb_lo * KT, vec, vr);
+  kmm_stage_v<1>(vr, Vs);
+  gd4 ai[G][2];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) ai[g][cb] = gd4{0.0, 0.0, 0.0, 0.0};
+  double idq[4];  // B_q[k = l >> 4][n = l & 15] = (n == 4 q + k)
+#pragma unroll
+  for (int q = 0; q < 4; ++q) idq[q] = (lane & 15) == 4 * q + (lane >> 4) ? 1.0 : 0.0;
+  __syncthreads();
+  double* Wtp = Wt + (size_t)blockIdx.y * n * nvc;
+  for (int jb = jb_lo; jb < jb_hi; ++jb) {
+    const int j0 = jb * KT;
+    const bool more = jb + 1 < jb_hi;
+    if (more) kmm_fetch_v<1>(V, ldv, n, nvc, j0 + KT, vec, vr);  // lands under the tiles
+    gd4 aj[2] = {gd4{0.0, 0.0, 0.0, 0.0}, gd4{0.0, 0.0, 0.0, 0.0}};
+    const double* va = Vs + (lane & 15) * KMM_VS + 32 * wr + (lane >> 4);
+    auto kmm_sym_tile = [&](int g) {
+      const int ib = ib0 + g;
+      if (ib > jb) return;  // the band's own super-block: I <= J only (and I < nblk with it)
+      gd4 v[2][2];
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) v[rb][cb] = gd4{0.0, 0.0, 0.0, 0.0};
+      if (ib == jb)
+        gram_tile<SC, true, MIX, PROD>(kp, S, gR, gC, nrm, nrm, nblk16, nblk16, j0, ib * KT, tabs, v, tmw);
+      else
+        gram_tile<SC, false, MIX, PROD>(kp, S, gR, gC, nrm, nrm, nblk16, nblk16, j0, ib * KT, tabs, v, tmw);
+      __builtin_amdgcn_sched_barrier(0);  // (no operand of the products is loaded above: registers)
+      // Out[I]^T += V[J]^T T, as kmatmul_kernel
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double a = va[16 * rb + 4 * q];
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb)
+            ai[0][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, v[rb][cb][q], ai[0][cb], 0, 0, 0);
+        }
+      if (ib == jb) return;
+      __builtin_amdgcn_sched_barrier(0);
+      // Out[J]^T += V[I]^T T^T: block (rb, cb) transposed is block (cb, rb) of T^T, whose rows
+      // (the summed points) are I's 32 wc + 16 cb + [0, 16) and whose columns are J's
+      // 32 wr + 16 rb + [0, 16)
+      const double* vi = Vb + (g * 16 + (lane & 15)) * KMM_VS + 32 * wc + (lane >> 4);
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          gd4 t = gd4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            t = __builtin_amdgcn_mfma_f64_16x16x4f64(v[rb][cb][q], idq[q], t, 0, 0, 0);
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            aj[rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(vi[16 * cb + 4 * q], t[q], aj[rb], 0, 0, 0);
+        }
+    };
+    // (a loop at run time: one copy of the tile code, whose accumulator is ai[0] -- the G
+    // accumulators rotate by one per step, G steps per J)
+#pragma nounroll
+    for (int g = 0; g < G; ++g) {
+      kmm_sym_tile(g);
+      const gd4 r0 = ai[0][0], r1 = ai[0][1];
+#pragma unroll
+      for (int h = 0; h + 1 < G; ++h) {
+        ai[h][0] = ai[h + 1][0];
+        ai[h][1] = ai[h + 1][1];
+      }
+      ai[G - 1][0] = r0;
+      ai[G - 1][1] = r1;
+    }
+    // the two column halves' sums of a row half: wave (wr, 1) hands Out[J] to (wr, 0)
+    double* rj = red + wr * 512 + lane;
+    if (wc == 1) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rj[(rb * 4 + q) * 64] = aj[rb][q];
+    }
+    __syncthreads();  // the block's V is read, the hand-over written
+    if (more) kmm_stage_v<1>(vr, Vs);
+    if (wc == 0) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = j0 + 32 * wr + 16 * rb + (lane & 15);
+          const int c = (lane >> 4) + 4 * q;
+          if (i < n && c < nvc) Wtp[(size_t)c * n + i] = aj[rb][q] + rj[(rb * 4 + q) * 64];
+        }
+    }
+    __syncthreads();
+  }
+  // Out[I]: the two row halves' sums of a column half, as kmatmul_kernel, over the band's V
+  double* rd = Vb + wc * (G * 512) + lane;  // 1024 G doubles of the 1056 G
+  if (wr == 1) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rd[((g * 2 + cb) * 4 + q) * 64] = ai[g][cb][q];
+  }
+  __syncthreads();
+  if (wr == 0) {
+    double* Wdp = Wd + ((size_t)blockIdx.y * nslab + blockIdx.x) * ((size_t)G * KT * nvc);
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int il = g * KT + 32 * wc + 16 * cb + (lane & 15);
+          const int c = (lane >> 4) + 4 * q;
+          if (c < nvc) Wdp[(size_t)c * (G * KT) + il] = ai[g][cb][q] + rd[((g * 2 + cb) * 4 + q) * 64];
+        }
+  }
+}
+
+// Out[i, c] (+)= the Out[J] partials of this launch's bands that reach row i (band order), then
+// the Out[I] partials of i's own band (slab order) where that band is in this launch
+__global__ __launch_bounds__(256) void kmm_sym_reduce_kernel(
+    const double* __restrict__ Wt, const double* __restrict__ Wd, int band0, int nbands, int nslab,
+    int G, int n, int nvc, double* __restrict__ Out, size_t ldo, int accum) {
+  const size_t total = (size_t)n * nvc, wd = (size_t)G * KT * nvc;
+  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total;
+       t += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = t / n, i = t - c * n;
+    const int band = (int)(i / KT) / G;
+    if (band < band0) continue;  // every band of this launch starts below row i
+    const int np = min(nbands, band - band0 + 1);
+    double s = Wt[t];
+    for (int k = 1; k < np; ++k) s += Wt[(size_t)k * total + t];
+    if (band < band0 + nbands) {
+      const double* wp = Wd + (size_t)(band - band0) * nslab * wd + c * ((size_t)G * KT) +
+                         (i - (size_t)band * G * KT);
+      for (int k = 0; k < nslab; ++k) s += wp[(size_t)k * wd];
+    }
+    double* dst = Out + c * ldo + i;
+    *dst = accum ? *dst + s : s;
+  }
+}
+
+// one symmetric pass: columns [0, nvc <= 16) of V, a same-points form (o.na == o.nb, one set of
+// norms), the parts of g at part offset p0
+template <int SC, bool MIX, bool PROD>
+int kmm_sym_launch_g(gpr_ctx* ctx, const KmmOps& o, const KParams& g, int p0, const double* V,
+                     int ldv, int nvc, double* Out, int ldo, int accum) {
+  constexpr int G = kmm_sym_g<SC, MIX, PROD>();
+  const int S = o.S, n = o.na;
+  const int nblk = (n + KT - 1) / KT, nband = (nblk + G - 1) / G;
+  const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
+  // slabs of a launch's walks: GPR_KMM_SLABS, else two workgroups per CU, never more than the
+  // launch's longest walk has blocks
+  auto slabs_of = [&](int band0, int nb) {
+    const int want = ctx->kmm_slabs > 0 ? ctx->kmm_slabs : (2 * ncu + nb - 1) / nb;
+    return std::max(1, std::min(want, std::min(nblk - band0 * G, KMM_MAXS)));
+  };
+  const size_t wt = (size_t)std::min(nband, KMS_P) * n * nvc, wd1 = (size_t)G * KT * nvc;
+  size_t wd = 0;
+  for (int b0 = 0; b0 < nband; b0 += KMS_P) {
+    const int nb = std::min(KMS_P, nband - b0);
+    wd = std::max(wd, (size_t)nb * slabs_of(b0, nb) * wd1);
+  }
+  GPR_TRY(ensure_buf(ctx, ctx->dkmm, wt + wd));
+  double* Wt = ctx->dkmm;
+  double* Wd = Wt + wt;
+  const int vec = ((uintptr_t)V & 15) == 0 && (ldv & 1) == 0;
+  const double* gR = o.B + (size_t)p0 * o.nbB * S * 64;
+  const double* gC = o.A + (size_t)p0 * o.nbA * S * 64;
+  const double* nrm = o.nrmA + (size_t)p0 * o.nbA * 16;
+  const size_t lds =
+      sizeof(double) * ((G + 1) * 16 * KMM_VS + 1024 + 256 * g.nse + (PROD ? 16 * 256 : 0));
+  auto* kern = &kmatmul_sym_kernel<SC, MIX, PROD, G>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return set_err(ctx, GPR_E_HIP, "kernel_matmul: %zu bytes of LDS refused", lds);
+  for (int b0 = 0; b0 < nband; b0 += KMS_P) {
+    const int nb = std::min(KMS_P, nband - b0), slabs = slabs_of(b0, nb);
+    kern<<<dim3((unsigned)slabs, (unsigned)nb), 256, lds, ctx->stream>>>(
+        g, S, gR, gC, nrm, o.nbA, n, b0, slabs, V, (size_t)ldv, nvc, vec, Wt, Wd);
+    LAUNCH_CHECK(ctx);
+    const int blocks = (int)std::min<size_t>(((size_t)n * nvc + 255) / 256, 4096);
+    kmm_sym_reduce_kernel<<<blocks, 256, 0, ctx->stream>>>(Wt, Wd, b0, nb, slabs, G, n, nvc, Out,
+                                                           (size_t)ldo, accum || b0 > 0);
+    LAUNCH_CHECK(ctx);
+  }
+  return 0;
+}
+
+// one symmetric pass: columns [0, nvc <= 16) of V, a same-points form (o.na == o.nb, one set of
+// norms), the parts of g at part offset p0
+template <int SC>
+int kmm_sym_launch(gpr_ctx* ctx, const KmmOps& o, const KParams& g, int p0, const double* V,
+                   int ldv, int nvc, double* Out, int ldo, int accum) {
+  return kmixprod_dispatch_full(g.mix, g.prod, [&](auto mix, auto prod) {
+    return kmm_sym_launch_g<SC, decltype(mix)::value, decltype(prod)::value>(ctx, o, g, p0, V, ldv,
+                                                                             nvc, Out, ldo, accum);
+  });
+}
+
 }  // namespace
 
 int kmm_prepare(gpr_ctx* ctx, const KParams& kpx, const double* dXa, int na, const double* dXb,
@@ -293,6 +555,12 @@ int kmm_apply(gpr_ctx* ctx, const KmmOps& o, const double* dV, int nv, int ldv, 
       }
       // k-steps compiled in for d <= 8, walked at run time above (zero steps change no bit)
       const int accum = p0 > 0;
+      if (ctx->kmm_sym && o.same != GPR_CROSS && nvc <= 16) {  // (wider passes: MFMA-bound)
+        if (o.S == 1) GPR_TRY((kmm_sym_launch<1>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum)));
+        else if (o.S == 2) GPR_TRY((kmm_sym_launch<2>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum)));
+        else GPR_TRY((kmm_sym_launch<0>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum)));
+        continue;
+      }
       if (o.S == 1) GPR_TRY((kmm_launch_nv<1>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum)));
       else if (o.S == 2) GPR_TRY((kmm_launch_nv<2>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum)));
       else GPR_TRY((kmm_launch_nv<0>(ctx, o, g, p0, V, ldv, nvc, Out, ldo, accum)));

@@ -8,6 +8,7 @@ column-major (a torch tensor of shape (cols, rows)).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 from typing import Optional, Sequence, Tuple
@@ -426,15 +427,29 @@ def kernel(cov: AbstractKernel, hp, x, xp=None, eps: float = EPS_DEFAULT,
     return ctx.host(K) if host else K
 
 
+@contextlib.contextmanager
+def _kmm_sym(ctx: Context, symmetric: bool):
+    """GPR_KMM_SYM set to ``symmetric`` for one call and restored."""
+    knob = ctx.get_knob("GPR_KMM_SYM")
+    ctx.set_knob("GPR_KMM_SYM", 1 if symmetric else 0)
+    try:
+        yield
+    finally:
+        ctx.set_knob("GPR_KMM_SYM", knob)
+
+
 def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAULT,
                   ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
-                  host: bool = True):
+                  host: bool = True, symmetric: bool = False):
     """kernel(cov, hp, x, xp) @ V without the matrix: the N x M kernel is evaluated tile by tile in
     registers (gpr_kernel_matmul), so memory stays linear in N + M.  ``xp`` selects the form by
     kernel()'s rule (None: eps per stationary part plus noise, the matrix a fit factors; ``xp is
     x``: eps, no noise; else a cross kernel).  V: M or M x nv.  A device V is column-major with
     its rows as the leading dimension (nv x ldv tensor, ldv >= M), and so is ``out`` (nv x ldo,
-    ldo >= N), which is then returned as it is."""
+    ldo >= N), which is then returned as it is.  ``symmetric``: a same-points form evaluates only
+    the tiles on and above K's diagonal and uses each twice (the knob GPR_KMM_SYM, set for this
+    call and restored; passes of 17 to 64 columns keep the full evaluation); ValueError with a
+    cross ``xp``."""
     ctx = ctx or default_context()
     dx = ctx.colmajor(x)
     n = dx.shape[0]
@@ -448,13 +463,16 @@ def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAU
     else:
         dxp = ctx.colmajor(xp)
         m, same = dxp.shape[0], _lib.GPR_CROSS
+    if symmetric and same == _lib.GPR_CROSS:
+        raise ValueError("symmetric=True needs a same-points form (xp None or xp is x)")
     dV = ctx.colmajor(V)
     vec = dV.ndim == 1
     nv = 1 if vec else dV.shape[0]
     O = out if out is not None else (ctx.empty(n) if vec else ctx.empty(nv, n))
-    ctx.check(lib.gpr_kernel_matmul(ctx.h, kinds, nk, hpp, d, _ptr(dx), n, _ptr(dxp), m, same, eps,
-                                    _ptr(dV), nv, dV.shape[-1], _ptr(O), O.shape[-1]),
-              "gpr_kernel_matmul")
+    with _kmm_sym(ctx, symmetric):
+        ctx.check(lib.gpr_kernel_matmul(ctx.h, kinds, nk, hpp, d, _ptr(dx), n, _ptr(dxp), m, same,
+                                        eps, _ptr(dV), nv, dV.shape[-1], _ptr(O), O.shape[-1]),
+                  "gpr_kernel_matmul")
     return ctx.host(O) if host and out is None else O
 
 
@@ -507,13 +525,14 @@ def kernel_grad_form(cov: AbstractKernel, hp, x, A, B, eps: float = EPS_DEFAULT,
 
 def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: float = 1e-6,
                   maxit: Optional[int] = None, log_scale: bool = False,
-                  eps: float = EPS_DEFAULT, precond_rank: int = 0):
+                  eps: float = EPS_DEFAULT, precond_rank: int = 0, symmetric: bool = False):
     """The gradient of the negative log marginal likelihood without K, K^{-1} or a factorisation
     (gpr_mll_grad_free): one solve_cg call for [alpha | K^{-1} Z], then kernel_grad_form; the
     trace term is Hutchinson's estimate over the probes Z (N x m; default: ``probes`` standard-
     normal columns from the library's generator at ``seed``, 0 <= seed < 2^31).  ``precond_rank``:
     the rank of the solve's pivoted-Cholesky preconditioner (the knob GPR_CG_PRECOND, set for this
-    call and restored).  Returns (g, iters, relres)."""
+    call and restored).  ``symmetric``: the solve's products by kernel_matmul's symmetric route.
+    Returns (g, iters, relres)."""
     ctx = md.ctx
     kinds, nk = _kinds_arr(md.covar)
     hpa, hpp = _hp_arr(md.params)
@@ -529,12 +548,13 @@ def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: fl
     knob = ctx.get_knob("GPR_CG_PRECOND")
     ctx.set_knob("GPR_CG_PRECOND", int(precond_rank))
     try:
-        ctx.check(lib.gpr_mll_grad_free(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n,
-                                        _ptr(md.dsample()), eps, m, int(seed),
-                                        _ptr(dZ), tol, md.n if maxit is None else int(maxit),
-                                        1 if log_scale else 0,
-                                        g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                        ctypes.byref(iters), relres), "gpr_mll_grad_free")
+        with _kmm_sym(ctx, symmetric):
+            ctx.check(lib.gpr_mll_grad_free(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n,
+                                            _ptr(md.dsample()), eps, m, int(seed),
+                                            _ptr(dZ), tol, md.n if maxit is None else int(maxit),
+                                            1 if log_scale else 0,
+                                            g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            ctypes.byref(iters), relres), "gpr_mll_grad_free")
     finally:
         ctx.set_knob("GPR_CG_PRECOND", knob)
     return g, iters.value, np.array(relres[:])
@@ -958,14 +978,16 @@ def predict_mean_from(md: GPRModel, alpha, xp, eps: float = EPS_DEFAULT) -> np.n
 
 
 def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = None,
-             eps: float = EPS_DEFAULT, precond_rank: int = 0, precond_rtol: float = 0.0):
+             eps: float = EPS_DEFAULT, precond_rank: int = 0, precond_rtol: float = 0.0,
+             symmetric: bool = False):
     """K^{-1} B by conjugate gradients on the matrix a fit factors, every product matrix-free
     (gpr_solve_cg): memory O(N), no preconditioner beyond K's constant diagonal, iterations ~
     sqrt(cond(K)).  B defaults to md.y; maxit to N.  Returns (alpha, iters, relres) with relres
     the true ||b - K alpha|| / ||b|| per column; reaching maxit is reported, not raised.
     ``precond_rank`` > 0 (at most 256): the pivoted-Cholesky preconditioner of that rank
     (gpr_solve_pcg, ``precond_rtol`` its early stop), which cuts the iterations at small sigma_n; 0
-    is the plain call."""
+    is the plain call.  ``symmetric``: every product by kernel_matmul's symmetric route (up to 16
+    columns per pass)."""
     ctx = md.ctx
     kinds, nk = _kinds_arr(md.covar)
     hpa, hpp = _hp_arr(md.params)
@@ -975,15 +997,16 @@ def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = Non
     iters = ctypes.c_int(0)
     relres = (ctypes.c_double * nrhs)()
     maxit = md.n if maxit is None else int(maxit)
-    if precond_rank:
-        ctx.check(lib.gpr_solve_pcg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB), nrhs,
-                                    dB.shape[-1], eps, tol, maxit, int(precond_rank),
-                                    float(precond_rtol), _ptr(X), md.n, ctypes.byref(iters), relres,
-                                    None), "gpr_solve_pcg")
-    else:
-        ctx.check(lib.gpr_solve_cg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB), nrhs,
-                                   dB.shape[-1], eps, tol, maxit,
-                                   _ptr(X), md.n, ctypes.byref(iters), relres), "gpr_solve_cg")
+    with _kmm_sym(ctx, symmetric):
+        if precond_rank:
+            ctx.check(lib.gpr_solve_pcg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB),
+                                        nrhs, dB.shape[-1], eps, tol, maxit, int(precond_rank),
+                                        float(precond_rtol), _ptr(X), md.n, ctypes.byref(iters),
+                                        relres, None), "gpr_solve_pcg")
+        else:
+            ctx.check(lib.gpr_solve_cg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB),
+                                       nrhs, dB.shape[-1], eps, tol, maxit,
+                                       _ptr(X), md.n, ctypes.byref(iters), relres), "gpr_solve_cg")
     return ctx.host(X), iters.value, np.array(relres[:])
 
 

@@ -243,6 +243,15 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *   GPR_KMM_SLABS      0  gpr_kernel_matmul: slabs the summed points are cut into per 64 output
  *                         points (each a workgroup; their partial products are added in slab
  *                         order); 0 auto: the fewest that give two workgroups per CU, at most 64
+ *   GPR_KMM_SYM        0  gpr_kernel_matmul and everything built on it (the same-object posterior
+ *                         mean, gpr_solve_cg / gpr_solve_pcg, gpr_mll_grad_free): 1 sends every
+ *                         pass of a same-points form (GPR_SELF, GPR_SAME_OBJECT) with at most 16
+ *                         columns to the symmetric kernel, which evaluates only the 64 x 64 tiles
+ *                         on and above K(x, x)'s diagonal and uses each off-diagonal tile twice
+ *                         (transposed in registers); there GPR_KMM_SLABS cuts each band's walk.
+ *                         Another summation order, the same elements; workspace stays linear in
+ *                         n (at most 64 n nv doubles).  0: every tile, every existing bit.  Wider
+ *                         passes and cross kernels ignore it
  *   GPR_KGF_SLABS      0  gpr_kernel_grad_form: the same for its row blocks (the partial slots are
  *                         added in slab order); 0 auto
  *   GPR_MEAN_FREE     -1  gpr_predict, GPR_PREDICT_MEAN: the mean by the matrix-free product (1)
@@ -291,7 +300,7 @@ int gpr_kernel(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
  * GPR_SELF / GPR_SAME_OBJECT need na == nb and ignore dXb (GPR_SELF is the matrix gpr_fit
  * factors).  Workspace is linear in na + nb; nothing of size na nb is allocated.  No atomics:
  * two calls agree bit for bit (GPR_KMM_SLABS changes the summation order, nothing else).
- * K(x, x) is evaluated in full, without a symmetry saving.  Asynchronous on the context's
+ * K(x, x) is evaluated in full unless GPR_KMM_SYM asks for the symmetric route.  Asynchronous on the context's
  * stream.  GPR_E_ARG, naming the argument, before anything is written: a NULL pointer, na, nb
  * or nv < 1, ldv < nb, ldo < na, a same-object form with na != nb.  (No reference counterpart:
  * the reference always forms the matrix.) */
