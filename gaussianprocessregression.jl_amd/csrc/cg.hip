@@ -35,8 +35,15 @@
 // r.z and r.r, forms beta and p and writes the next slot.  The stop test stays on r.r, the freezing
 // and the two slots are the same.  With rank 0 none of this runs: the kernels above, in the order
 // above.
+//
+// GPR_KMM_PREC = 1 (a description the FP32 product kernel takes, kmatmul_f32.hip): iterative
+// refinement around the same recurrence -- x = 0, r = b; per outer step the recurrence on K~ d = r
+// (products with FP32 kernel evaluation) from d = 0 to the column's threshold, x += d, r = b - K x
+// by one FP64 product; an outer step that gains less than 4 x sends the rest of the call to FP64
+// products.  iters counts every product of either precision; relres stays the FP64 residual.
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "common.hpp"
 
@@ -245,6 +252,56 @@ __global__ __launch_bounds__(256) void cg_sum_kernel(const double* __restrict__ 
   if (threadIdx.x == 0) out[c] = s;
 }
 
+// ---- iterative refinement around the recurrence (GPR_KMM_PREC) --------------------------------
+// grid nrhs.  The start of an inner solve K d = r from d = 0: s = r.r (the partials of
+// cg_init_kernel); the column's stop threshold thr[c] = max(tol^2 b.b, floor2 s) -- floor2 = 2^-32:
+// ||r_in|| <= max(tol ||b|| / ||r||, 2^-16) ||r||; 0: the FP64 recurrence to tol -- and slot 0:
+// r.r = s, frozen when s <= thr (a column whose FP64 residual has met tol stays as it is)
+__global__ __launch_bounds__(256) void cg_refine_scalars_kernel(const double* __restrict__ part,
+                                                                int nblk, int nrhs, double tol2,
+                                                                double floor2,
+                                                                const double* __restrict__ bb,
+                                                                double* __restrict__ sc,
+                                                                double* __restrict__ thr) {
+  __shared__ double red[256];
+  const int c = blockIdx.x;
+  const double s =
+      cg_block_sum((int)threadIdx.x < nblk ? part[(size_t)c * CG_MAXB + threadIdx.x] : 0.0, red);
+  if (threadIdx.x == 0) {
+    const double t = fmax(tol2 * bb[c], floor2 * s);
+    thr[c] = t;
+    double* o = cg_slot(sc, 0, nrhs, c);
+    o[0] = s;
+    o[1] = s <= t ? 1.0 : 0.0;
+  }
+}
+
+// grid (nblk, nrhs).  x += d
+__global__ __launch_bounds__(256) void cg_add_kernel(const double* __restrict__ D, int n,
+                                                     double* __restrict__ X, size_t ldx) {
+  const int c = blockIdx.y;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    X[(size_t)c * ldx + i] += D[(size_t)c * n + i];
+}
+
+// grid (nblk, nrhs).  r = b - q, stored; part[c][blk] = partial ||r||^2
+__global__ __launch_bounds__(256) void cg_resid_store_kernel(const double* __restrict__ B,
+                                                             size_t ldb,
+                                                             const double* __restrict__ Q, int n,
+                                                             double* __restrict__ R,
+                                                             double* __restrict__ part) {
+  __shared__ double red[256];
+  const int c = blockIdx.y;
+  double s = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double r = B[(size_t)c * ldb + i] - Q[(size_t)c * n + i];
+    R[(size_t)c * n + i] = r;
+    s = fma(r, r, s);
+  }
+  s = cg_block_sum(s, red);
+  if (threadIdx.x == 0) part[(size_t)c * CG_MAXB + blockIdx.x] = s;
+}
+
 // K's constant diagonal in the GPR_SELF form
 double cg_diagonal(const KParams& kp) {
   double dg = kp.has_noise ? kp.noise2 : 0.0, term = 1.0;
@@ -290,32 +347,28 @@ int cg_solve(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d, c
   const bool pre = rank > 0;
   const double dinv = pre ? 1.0 : 1.0 / cg_diagonal(kp), tol2 = tol * tol;
   const size_t nn = (size_t)n * nrhs, np = (size_t)nrhs * CG_MAXB;
-  // r | p | q | p.q partials | r.r partials | two scalar slots | b.b | the final residuals
-  // (| z | r.z partials, preconditioned)
-  GPR_TRY(ensure_buf(ctx, ctx->dcg, 3 * nn + 2 * np + 6 * (size_t)nrhs +
-                                        (pre ? nn + (size_t)nrhs * PCH_MAXB : 0)));
-  double* R = ctx->dcg;
-  double *P = R + nn, *Q = P + nn, *pq = Q + nn, *rr = pq + np, *sc = rr + np;
-  double *bb = sc + 4 * (size_t)nrhs, *res = bb + nrhs;
-  double *Z = res + nrhs, *rz = Z + nn;
-  PinnedDoubles host;
-  HIP_TRY(ctx, hipHostMalloc((void**)&host.p, sizeof(double) * 2 * nrhs, hipHostMallocDefault));
   PcholOps pc{};
   if (pre) GPR_TRY(pchol_prepare(ctx, kp, dX, n, rank, rtol, nrhs, &pc));
   if (rank_out) *rank_out = pre ? pc.k : 0;
   int nz = 0;
   KmmOps ops;
-  GPR_TRY(kmm_prepare(ctx, kp, dX, n, nullptr, n, GPR_SELF, &ops));
+  GPR_TRY(kmm_prepare(ctx, kp, dX, n, nullptr, n, GPR_SELF, &ops, true));
+  const bool mixed = ops.fa != nullptr;  // GPR_KMM_PREC, a description its kernel takes
+  // r | p | q | p.q partials | r.r partials | two scalar slots | b.b | the final residuals
+  // (| z | r.z partials, preconditioned) (| d | the FP64 residual | thresholds, refined)
+  const size_t npre = pre ? nn + (size_t)nrhs * PCH_MAXB : 0;
+  GPR_TRY(ensure_buf(ctx, ctx->dcg, 3 * nn + 2 * np + 6 * (size_t)nrhs + npre +
+                                        (mixed ? 2 * nn + nrhs : 0)));
+  double* R = ctx->dcg;
+  double *P = R + nn, *Q = P + nn, *pq = Q + nn, *rr = pq + np, *sc = rr + np;
+  double *bb = sc + 4 * (size_t)nrhs, *res = bb + nrhs;
+  double *Z = res + nrhs, *rz = Z + nn;
+  double *Dx = res + nrhs + npre, *Ro = Dx + nn, *thr = Ro + nn;
+  PinnedDoubles host;
+  HIP_TRY(ctx, hipHostMalloc((void**)&host.p, sizeof(double) * 2 * nrhs, hipHostMallocDefault));
   const int nblk = std::max(1, std::min(CG_MAXB, (n + 1023) / 1024));
   const dim3 grid((unsigned)nblk, (unsigned)nrhs);
   hipStream_t st = ctx->stream;
-  cg_init_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, n, dinv, dXout, (size_t)ldx, R, P, rr);
-  cg_init_scalars_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, nrhs, tol2, sc, bb);
-  if (pre) {
-    GPR_TRY(pchol_apply(ctx, pc, R, nrhs, Z, rz, &nz));
-    pcg_start_kernel<<<grid, 256, 0, st>>>(rz, nz, nrhs, sc, n, Z, P);
-  }
-  LAUNCH_CHECK(ctx);
   // the stop test reads the slot's (r.r, frozen) pairs: every column frozen
   auto all_frozen = [&](int slot, bool* done) {
     HIP_TRY(ctx, hipMemcpyAsync(host.p, cg_slot(sc, slot, nrhs, 0), sizeof(double) * 2 * nrhs,
@@ -327,30 +380,101 @@ int cg_solve(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d, c
     return 0;
   };
   int it = 0;
-  bool done = false;
-  GPR_TRY(all_frozen(0, &done));
-  while (!done && it < maxit) {
-    const int slot = it & 1;
-    GPR_TRY(kmm_apply(ctx, ops, P, nrhs, n, Q, n));
-    cg_dot_kernel<<<grid, 256, 0, st>>>(P, Q, n, pq);
-    cg_step_xr_kernel<<<grid, 256, 0, st>>>(pq, nblk, nrhs, slot, sc, dinv, n, P, Q, dXout,
-                                            (size_t)ldx, R, rr);
+  // the recurrence from R, P and slot 0 as initialised, into Xd: products of precision prec
+  // (kmm_apply's), a column frozen at r.r <= t2 stop[c]; every product counts in it, capped at maxit
+  auto recur = [&](double* Xd, size_t ldxd, const double* stop, double t2, int prec) {
     if (pre) {
       GPR_TRY(pchol_apply(ctx, pc, R, nrhs, Z, rz, &nz));
-      pcg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, rz, nz, nrhs, slot, sc, bb, tol2, n, Z, P);
-    } else {
-      cg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, nrhs, slot, sc, bb, tol2, dinv, n, R, P);
+      pcg_start_kernel<<<grid, 256, 0, st>>>(rz, nz, nrhs, sc, n, Z, P);
     }
     LAUNCH_CHECK(ctx);
-    ++it;
-    GPR_TRY(all_frozen(it & 1, &done));
+    int k = 0;
+    bool done = false;
+    GPR_TRY(all_frozen(0, &done));
+    while (!done && it < maxit) {
+      const int slot = k & 1;
+      GPR_TRY(kmm_apply(ctx, ops, P, nrhs, n, Q, n, prec));
+      cg_dot_kernel<<<grid, 256, 0, st>>>(P, Q, n, pq);
+      cg_step_xr_kernel<<<grid, 256, 0, st>>>(pq, nblk, nrhs, slot, sc, dinv, n, P, Q, Xd, ldxd, R,
+                                              rr);
+      if (pre) {
+        GPR_TRY(pchol_apply(ctx, pc, R, nrhs, Z, rz, &nz));
+        pcg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, rz, nz, nrhs, slot, sc, stop, t2, n, Z, P);
+      } else {
+        cg_step_p_kernel<<<grid, 256, 0, st>>>(rr, nblk, nrhs, slot, sc, stop, t2, dinv, n, R, P);
+      }
+      LAUNCH_CHECK(ctx);
+      ++k;
+      ++it;
+      GPR_TRY(all_frozen(k & 1, &done));
+    }
+    return 0;
+  };
+  bool have_res = false;  // res holds ||b - K x||^2 of the x returned
+  if (!mixed) {
+    cg_init_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, n, dinv, dXout, (size_t)ldx, R, P, rr);
+    cg_init_scalars_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, nrhs, tol2, sc, bb);
+    GPR_TRY(recur(dXout, (size_t)ldx, bb, tol2, 0));
+  } else {
+    // Iterative refinement: x = 0, r = b; per outer step the recurrence on K~ d = r (the FP32
+    // kernel's matrix) to the column's threshold, x += d, r = b - K x by one FP64 product.  A
+    // column is done when that residual meets tol.  An outer step that takes a column's residual
+    // down by less than 4 x (cond_2(K) ||K~ - K|| / ||K|| is not small) sends the rest of the call
+    // to FP64 products: the recurrence on K d = r to tol.
+    ctx->cg_outer = ctx->cg_f64 = 0;
+    cg_init_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, n, dinv, dXout, (size_t)ldx, Ro, P, rr);
+    cg_sum_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, bb);
+    cg_sum_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, res);
+    LAUNCH_CHECK(ctx);
+    std::vector<double> prev(nrhs), b2(nrhs);
+    auto read_res = [&]() {  // (bb and res are adjacent: one copy)
+      HIP_TRY(ctx, hipMemcpyAsync(host.p, bb, sizeof(double) * 2 * nrhs, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+      return 0;
+    };
+    GPR_TRY(read_res());
+    for (int c = 0; c < nrhs; ++c) b2[c] = host.p[c], prev[c] = host.p[nrhs + c];
+    have_res = true;
+    bool f64 = false;
+    for (;;) {
+      bool active = false;
+      for (int c = 0; c < nrhs; ++c) active = active || prev[c] > tol2 * b2[c];
+      if (!active || it >= maxit) break;
+      cg_init_kernel<<<grid, 256, 0, st>>>(Ro, (size_t)n, n, dinv, Dx, (size_t)n, R, P, rr);
+      cg_refine_scalars_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, nrhs, tol2, f64 ? 0.0 : 0x1p-32, bb,
+                                                     sc, thr);
+      const int it0 = it;
+      GPR_TRY(recur(Dx, (size_t)n, thr, 1.0, f64 ? 0 : 1));
+      if (f64) ctx->cg_f64 += it - it0;
+      cg_add_kernel<<<grid, 256, 0, st>>>(Dx, n, dXout, (size_t)ldx);
+      LAUNCH_CHECK(ctx);
+      ++ctx->cg_outer;
+      have_res = false;
+      if (it >= maxit) break;
+      GPR_TRY(kmm_apply(ctx, ops, dXout, nrhs, ldx, Q, n, 0));
+      ++it;
+      ++ctx->cg_f64;
+      cg_resid_store_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, Q, n, Ro, rr);
+      cg_sum_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, res);
+      LAUNCH_CHECK(ctx);
+      GPR_TRY(read_res());
+      have_res = true;
+      for (int c = 0; c < nrhs; ++c) {
+        const double now = host.p[nrhs + c];
+        // (a column the step has brought to tol is done, whatever the step gained)
+        if (now > tol2 * b2[c] && now > prev[c] / 16.0) f64 = true;
+        prev[c] = now;
+      }
+    }
   }
   if (iters) *iters = it;
   if (relres) {  // the true residual
-    GPR_TRY(kmm_apply(ctx, ops, dXout, nrhs, ldx, Q, n));
-    cg_resid_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, Q, n, rr);
-    cg_sum_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, res);
-    LAUNCH_CHECK(ctx);
+    if (!have_res) {
+      GPR_TRY(kmm_apply(ctx, ops, dXout, nrhs, ldx, Q, n, 0));
+      cg_resid_kernel<<<grid, 256, 0, st>>>(dB, (size_t)ldb, Q, n, rr);
+      cg_sum_kernel<<<nrhs, 256, 0, st>>>(rr, nblk, res);
+      LAUNCH_CHECK(ctx);
+    }
     // (bb and res are adjacent: one copy)
     HIP_TRY(ctx, hipMemcpyAsync(host.p, bb, sizeof(double) * 2 * nrhs, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));

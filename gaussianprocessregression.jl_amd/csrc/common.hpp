@@ -331,6 +331,11 @@ struct gpr_ctx {
   int kmm_slabs = 0;            // GPR_KMM_SLABS: slabs of xb per 64 output points (0 auto)
   int kmm_sym = 0;              // GPR_KMM_SYM: same-points passes of <= 16 columns evaluate only the
                                 // tiles I <= J of K(x, x) (kmatmul_sym_kernel); 0: every tile
+  int kmm_prec = 0;             // GPR_KMM_PREC: 1 evaluates K's profiles in FP32 inside the matrix-free
+                                // product (kmatmul_f32.hip) and refines the CG solves (cg.hip)
+  DevBuf dkmf;                  // its FP32 points of xa and xb (floats, two per double)
+  int cg_outer = 0, cg_f64 = 0; // the last refined solve's outer steps and FP64 products
+                                // (GPR_CG_STAT_OUTER, GPR_CG_STAT_F64: for reading)
   // the pivoted-Cholesky preconditioner (pchol.hip): the build's state (residual diagonal, pivot
   // partials, pivots, flag) | the solve's factor L, C = delta I + L^T L and t | the slab partials
   // of L^T R | a Periodic part's unit features
@@ -514,11 +519,37 @@ struct KmmOps {
   const double *xa, *xb;  // scaled points (all parts)
   const double *A, *nrmA, *B, *nrmB;
   int nbA, nbB;
+  // the FP32 route (kmatmul_f32.hip; null unless GPR_KMM_PREC is on and the description inside its
+  // envelope): per part and point the centred scaled points rounded to FP32, [part][point][fdp],
+  // points padded with zeros to a multiple of 64 (fpa, fpb), fdp = d rounded up to a multiple of 4
+  const float *fa = nullptr, *fb = nullptr;
+  int fpa = 0, fpb = 0, fdp = 0;
 };
+// f32: the caller will apply the FP32 route where GPR_KMM_PREC asks for it (gpr_kernel_matmul and
+// the CG solves; every other caller keeps the FP64 kernels whatever the knob says)
 int kmm_prepare(gpr_ctx* ctx, const KParams& kp, const double* dXa, int na, const double* dXb,
-                int nb, int same, KmmOps* o);
+                int nb, int same, KmmOps* o, bool f32 = false);
+// prec: -1 as prepared (the FP32 route where kmm_prepare made its operands), 0 the FP64 kernels
 int kmm_apply(gpr_ctx* ctx, const KmmOps& o, const double* dV, int nv, int ldv, double* dOut,
-              int ldo);
+              int ldo, int prec = -1);
+// The slab plan of one pass of a product kernel (grid (nta, slabs)): slabs of slab_blocks 64-point
+// blocks of xb -- GPR_KMM_SLABS, else the fewest that give two workgroups per CU; with more than
+// one slab the kernel writes partials to ctx->dkmm (grown here) and kmm_reduce_slabs adds them
+struct KmmSlabPlan {
+  int nta, slabs, slab_blocks, vec, accum;  // vec: V allows 16-byte loads; accum: the kernel's
+  double* dst;                              // the kernel's output, its ld and slab stride
+  size_t ldd, stride;
+};
+int kmm_slab_plan(gpr_ctx* ctx, int na, int nb, const double* V, int ldv, int nvc, double* Out,
+                  int ldo, int accum, KmmSlabPlan* pl);
+// Out (+)= the slab partials of ctx->dkmm (na x nvc each, ld na) in slab order
+int kmm_reduce_slabs(gpr_ctx* ctx, int slabs, int na, int nvc, double* Out, int ldo, int accum);
+// kmatmul_f32.hip: the product with each stationary part's profile evaluated in FP32 (GPR_KMM_PREC).
+// Sums of SquaredExp / Matern / WhiteNoise parts: no Periodic part, no product term.
+inline bool kmm_f32_takes(const KParams& kp) { return kp.nper == 0 && !kp.prod; }
+int kmm_f32_prepare(gpr_ctx* ctx, KmmOps* o);
+int kmm_f32_apply(gpr_ctx* ctx, const KmmOps& o, const double* dV, int nv, int ldv, double* dOut,
+                  int ldo);
 // pchol.hip: the rank-k partial pivoted Cholesky L (n x k, ldl) of the noise-free cross-form kernel
 // K_c of (kp, x), one launch per step; piv (host, may be null) gets the 0-based pivots and
 // *rank_out the rank reached (< rank when the largest residual diagonal fell to rtol n c)

@@ -310,12 +310,16 @@ const Knob kKnobs[] = {
     {"GPR_REMOVE_SWEEP", &gpr_ctx::remove_sweep, nullptr},
     {"GPR_KMM_SLABS", &gpr_ctx::kmm_slabs, nullptr},
     {"GPR_KMM_SYM", &gpr_ctx::kmm_sym, nullptr},
+    {"GPR_KMM_PREC", &gpr_ctx::kmm_prec, nullptr},
+    {"GPR_CG_STAT_OUTER", &gpr_ctx::cg_outer, nullptr},
+    {"GPR_CG_STAT_F64", &gpr_ctx::cg_f64, nullptr},
     {"GPR_KGF_SLABS", &gpr_ctx::kgf_slabs, nullptr},
     {"GPR_MEAN_FREE", &gpr_ctx::mean_free, nullptr},
     {"GPR_CG_PRECOND", &gpr_ctx::cg_precond, nullptr},
 };
 
 void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
+  if (k.ip == &gpr_ctx::cg_outer || k.ip == &gpr_ctx::cg_f64) return;  // statistics: read only
   if (k.ip) {
     int iv = (int)v;
     if (k.ip == &gpr_ctx::dag_zlag) iv = std::max(0, iv);
@@ -325,7 +329,7 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
     if (k.ip == &gpr_ctx::pgrad_slab) iv = (std::max(iv, 64) + 63) / 64 * 64;
     if (k.ip == &gpr_ctx::kmm_slabs || k.ip == &gpr_ctx::kgf_slabs) iv = std::max(0, iv);
     if (k.ip == &gpr_ctx::cg_precond) iv = std::max(0, std::min(iv, 256));
-    if (k.ip == &gpr_ctx::kmm_sym) iv = iv != 0;
+    if (k.ip == &gpr_ctx::kmm_sym || k.ip == &gpr_ctx::kmm_prec) iv = iv != 0;
     ctx->*k.ip = iv;
   } else {
     ctx->*k.dp = v;
@@ -340,6 +344,7 @@ DevBuf gpr_ctx::*const kWorkspaces[] = {
     &gpr_ctx::dgc,    &gpr_ctx::dpadA,    &gpr_ctx::dpadB,      &gpr_ctx::dagb,  &gpr_ctx::deig,
     &gpr_ctx::ddc,    &gpr_ctx::dtri,     &gpr_ctx::dkmm,       &gpr_ctx::dcg,
     &gpr_ctx::dgf,    &gpr_ctx::dpch,     &gpr_ctx::dpchl,      &gpr_ctx::dpchw, &gpr_ctx::dpchcs,
+    &gpr_ctx::dkmf,
 };
 
 const Knob* knob_find(const char* name) {
@@ -513,6 +518,8 @@ int gpr_set_knob(gpr_ctx_t ctx, const char* name, double value) {
   if (!ctx) return GPR_E_ARG;
   const Knob* k = knob_find(name);
   if (!k) return set_err(ctx, GPR_E_ARG, "unknown knob %s", name ? name : "(null)");
+  if (k->ip == &gpr_ctx::cg_outer || k->ip == &gpr_ctx::cg_f64)
+    return set_err(ctx, GPR_E_ARG, "%s is a statistic of the last refined solve: read only", name);
   knob_set(ctx, *k, value);
   // (the cached task list depends on GPR_DAG_ZLAG / RGROUP / RSKEW / RGROUP_MIN: the next
   // launch compares all four with the values the list was built from and rebuilds it)

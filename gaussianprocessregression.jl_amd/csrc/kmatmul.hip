@@ -53,47 +53,9 @@
 #include "common.hpp"
 #include "gram_tile.hpp"
 #include "kexp.hpp"
+#include "kmm_vstage.hpp"
 
 namespace {
-
-constexpr int KMM_VS = KT + 2;   // LDS stride (doubles) between the staged V block's columns
-constexpr int KMM_MAXS = 64;     // most slabs of one launch
-typedef double kv2 __attribute__((ext_vector_type(2)));
-
-// this thread's share of rows [j0, j0 + 64) x columns [0, 16 NVB) of V: row pair 2 (t & 31) of
-// columns (t >> 5) + 8 k.  Zero past nb or nvc, and nothing past them is read.
-template <int NVB>
-__device__ __forceinline__ void kmm_fetch_v(const double* __restrict__ V, size_t ldv, int nb,
-                                            int nvc, int j0, bool vec, kv2 (&r)[2 * NVB]) {
-  const int j = j0 + 2 * (int)(threadIdx.x & 31), cg = threadIdx.x >> 5;
-#pragma unroll
-  for (int k = 0; k < 2 * NVB; ++k) {
-    const int c = cg + 8 * k;
-    kv2 e = {0.0, 0.0};
-    if (c < nvc && j < nb) {
-      const double* src = V + (size_t)c * ldv + j;
-      if (j + 1 < nb) {
-        if (vec) {
-          e = *reinterpret_cast<const kv2*>(src);
-        } else {
-          e[0] = src[0];
-          e[1] = src[1];
-        }
-      } else {
-        e[0] = src[0];
-      }
-    }
-    r[k] = e;
-  }
-}
-
-template <int NVB>
-__device__ __forceinline__ void kmm_stage_v(const kv2 (&r)[2 * NVB], double* Vs) {
-  const int pr = threadIdx.x & 31, cg = threadIdx.x >> 5;
-#pragma unroll
-  for (int k = 0; k < 2 * NVB; ++k)
-    *reinterpret_cast<kv2*>(Vs + (cg + 8 * k) * KMM_VS + 2 * pr) = r[k];
-}
 
 // Two workgroups per CU (256 registers a lane), except the run-time-d tile with 64 columns of V,
 // whose operand chunks and 32 accumulators do not fit them (about 200 bytes a lane of scratch):
@@ -209,24 +171,11 @@ template <int SC, int NVB>
 int kmm_launch(gpr_ctx* ctx, const KmmOps& o, const KParams& g, int p0, const double* V, int ldv,
                int nvc, double* Out, int ldo, int accum) {
   const int S = o.S;
-  const int nta = (o.na + KT - 1) / KT, nbb = (o.nb + KT - 1) / KT;
-  const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
-  int slabs = ctx->kmm_slabs > 0 ? ctx->kmm_slabs : (2 * ncu + nta - 1) / nta;
-  slabs = std::max(1, std::min(slabs, std::min(nbb, KMM_MAXS)));
-  const int slab_blocks = (nbb + slabs - 1) / slabs;
-  slabs = (nbb + slab_blocks - 1) / slab_blocks;  // (no empty slab)
-  double* dst = Out;
-  size_t ldd = (size_t)ldo, stride = 0;
-  if (slabs > 1) {
-    GPR_TRY(ensure_buf(ctx, ctx->dkmm, (size_t)slabs * o.na * nvc));
-    dst = ctx->dkmm;
-    ldd = (size_t)o.na;
-    stride = (size_t)o.na * nvc;
-  }
-  const int vec = ((uintptr_t)V & 15) == 0 && (ldv & 1) == 0;
+  KmmSlabPlan pl;
+  GPR_TRY(kmm_slab_plan(ctx, o.na, o.nb, V, ldv, nvc, Out, ldo, accum, &pl));
   const size_t opB = (size_t)p0 * o.nbB * S * 64, opA = (size_t)p0 * o.nbA * S * 64;
   const size_t nB = (size_t)p0 * o.nbB * 16, nA = (size_t)p0 * o.nbA * 16;
-  const dim3 grid((unsigned)nta, (unsigned)slabs);
+  const dim3 grid((unsigned)pl.nta, (unsigned)pl.slabs);
   int rc = 0;
   kmixprod_dispatch_full(g.mix, g.prod, [&](auto mix, auto prod) {
     constexpr bool MIX = decltype(mix)::value, PROD = decltype(prod)::value;
@@ -240,17 +189,12 @@ int kmm_launch(gpr_ctx* ctx, const KmmOps& o, const KParams& g, int p0, const do
     }
     kern<<<grid, 256, lds, ctx->stream>>>(g, S, o.B + opB, o.A + opA, o.nrmB + nB, o.nrmA + nA,
                                           o.nbB, o.nbA, o.na, o.nb, o.same != GPR_CROSS,
-                                          slab_blocks, V, (size_t)ldv, nvc, vec, dst, ldd, stride,
-                                          slabs > 1 ? 0 : accum);
+                                          pl.slab_blocks, V, (size_t)ldv, nvc, pl.vec, pl.dst,
+                                          pl.ldd, pl.stride, pl.accum);
   });
   GPR_TRY(rc);
   LAUNCH_CHECK(ctx);
-  if (slabs > 1) {
-    const int blocks = (int)std::min<size_t>(((size_t)o.na * nvc + 255) / 256, 4096);
-    kmm_reduce_kernel<<<blocks, 256, 0, ctx->stream>>>(ctx->dkmm, slabs, o.na, nvc, Out,
-                                                       (size_t)ldo, accum);
-    LAUNCH_CHECK(ctx);
-  }
+  if (pl.slabs > 1) GPR_TRY(kmm_reduce_slabs(ctx, pl.slabs, o.na, nvc, Out, ldo, accum));
   return 0;
 }
 
@@ -525,8 +469,35 @@ int kmm_sym_launch(gpr_ctx* ctx, const KmmOps& o, const KParams& g, int p0, cons
 
 }  // namespace
 
+int kmm_slab_plan(gpr_ctx* ctx, int na, int nb, const double* V, int ldv, int nvc, double* Out,
+                  int ldo, int accum, KmmSlabPlan* pl) {
+  const int nta = (na + KT - 1) / KT, nbb = (nb + KT - 1) / KT;
+  const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
+  int slabs = ctx->kmm_slabs > 0 ? ctx->kmm_slabs : (2 * ncu + nta - 1) / nta;
+  slabs = std::max(1, std::min(slabs, std::min(nbb, KMM_MAXS)));
+  const int slab_blocks = (nbb + slabs - 1) / slabs;
+  slabs = (nbb + slab_blocks - 1) / slab_blocks;  // (no empty slab)
+  *pl = KmmSlabPlan{nta, slabs, slab_blocks, ((uintptr_t)V & 15) == 0 && (ldv & 1) == 0,
+                    slabs > 1 ? 0 : accum, Out, (size_t)ldo, 0};
+  if (slabs > 1) {
+    GPR_TRY(ensure_buf(ctx, ctx->dkmm, (size_t)slabs * na * nvc));
+    pl->dst = ctx->dkmm;
+    pl->ldd = (size_t)na;
+    pl->stride = (size_t)na * nvc;
+  }
+  return 0;
+}
+
+int kmm_reduce_slabs(gpr_ctx* ctx, int slabs, int na, int nvc, double* Out, int ldo, int accum) {
+  const int blocks = (int)std::min<size_t>(((size_t)na * nvc + 255) / 256, 4096);
+  kmm_reduce_kernel<<<blocks, 256, 0, ctx->stream>>>(ctx->dkmm, slabs, na, nvc, Out, (size_t)ldo,
+                                                     accum);
+  LAUNCH_CHECK(ctx);
+  return 0;
+}
+
 int kmm_prepare(gpr_ctx* ctx, const KParams& kpx, const double* dXa, int na, const double* dXb,
-                int nb, int same, KmmOps* o) {
+                int nb, int same, KmmOps* o, bool f32) {
   KParams kp = kparams_features(kpx);
   if (same == GPR_SAME_OBJECT) kp.has_noise = 0;  // eps per term, no noise (gpr_kernel's rule)
   GPR_TRY(launch_scaled_points(ctx, kpx, dXa, na, ctx->dxs));
@@ -536,11 +507,14 @@ int kmm_prepare(gpr_ctx* ctx, const KParams& kpx, const double* dXa, int na, con
   GPR_TRY(gram_prepare(ctx, kp, S, ctx->dxs, na, same ? nullptr : ctx->dxps.p, nb, same != 0, &g));
   *o = KmmOps{kp, na, nb, same, S, ctx->dxs, same ? ctx->dxs.p : ctx->dxps.p,
               g.A, g.nrmA, g.B, g.nrmB, g.nbA, g.nbB};
+  // GPR_KMM_PREC: the FP32 points beside them, where the description is inside that route's envelope
+  if (f32 && ctx->kmm_prec && kmm_f32_takes(kp)) GPR_TRY(kmm_f32_prepare(ctx, o));  // (after gram_prepare: its centres)
   return 0;
 }
 
 int kmm_apply(gpr_ctx* ctx, const KmmOps& o, const double* dV, int nv, int ldv, double* dOut,
-              int ldo) {
+              int ldo, int prec) {
+  if (prec != 0 && o.fa) return kmm_f32_apply(ctx, o, dV, nv, ldv, dOut, ldo);
   const KParams& kp = o.kp;
   for (int c0 = 0; c0 < nv; c0 += 64) {
     const int nvc = std::min(64, nv - c0);
@@ -590,7 +564,7 @@ int gpr_kernel_matmul(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp,
   if (ldv < nb) return set_err(ctx, GPR_E_ARG, "ldv=%d < nb=%d", ldv, nb);
   if (ldo < na) return set_err(ctx, GPR_E_ARG, "ldo=%d < na=%d", ldo, na);
   KmmOps o;
-  GPR_TRY(kmm_prepare(ctx, kp, dXa, na, dXb, nb, same, &o));
+  GPR_TRY(kmm_prepare(ctx, kp, dXa, na, dXb, nb, same, &o, true));
   return kmm_apply(ctx, o, dV, nv, ldv, dOut, ldo);
 }
 

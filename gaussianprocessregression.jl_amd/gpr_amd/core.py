@@ -438,9 +438,29 @@ def _kmm_sym(ctx: Context, symmetric: bool):
         ctx.set_knob("GPR_KMM_SYM", knob)
 
 
+@contextlib.contextmanager
+def _kmm_prec(ctx: Context, cov: AbstractKernel, precision: str, reduced: str):
+    """GPR_KMM_PREC set for one call and restored: 0 for "fp64", 1 for ``reduced`` ("fp32" for a
+    product, "mixed" for a solve).  ValueError for any other string, and for ``reduced`` with a
+    part the FP32 kernel does not take (Periodic, or a factor of a product), naming it."""
+    if precision not in ("fp64", reduced):
+        raise ValueError(f'precision must be "fp64" or "{reduced}", not {precision!r}')
+    if precision == reduced:
+        for part in cov.parts():
+            if part.KIND in (GPR_PER, GPR_MUL):
+                raise ValueError(f'precision="{reduced}" takes sums of SquaredExp, Matern and '
+                                 f"WhiteNoise parts: {part!r} is outside them")
+    knob = ctx.get_knob("GPR_KMM_PREC")
+    ctx.set_knob("GPR_KMM_PREC", 1 if precision == reduced else 0)
+    try:
+        yield
+    finally:
+        ctx.set_knob("GPR_KMM_PREC", knob)
+
+
 def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAULT,
                   ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
-                  host: bool = True, symmetric: bool = False):
+                  host: bool = True, symmetric: bool = False, precision: str = "fp64"):
     """kernel(cov, hp, x, xp) @ V without the matrix: the N x M kernel is evaluated tile by tile in
     registers (gpr_kernel_matmul), so memory stays linear in N + M.  ``xp`` selects the form by
     kernel()'s rule (None: eps per stationary part plus noise, the matrix a fit factors; ``xp is
@@ -449,7 +469,9 @@ def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAU
     ldo >= N), which is then returned as it is.  ``symmetric``: a same-points form evaluates only
     the tiles on and above K's diagonal and uses each twice (the knob GPR_KMM_SYM, set for this
     call and restored; passes of 17 to 64 columns keep the full evaluation); ValueError with a
-    cross ``xp``."""
+    cross ``xp``.  ``precision="fp32"``: every stationary part's profile is evaluated in FP32 and
+    widened into the same FP64 product (the knob GPR_KMM_PREC, set for this call and restored;
+    sums of SquaredExp, Matern and WhiteNoise parts, else ValueError)."""
     ctx = ctx or default_context()
     dx = ctx.colmajor(x)
     n = dx.shape[0]
@@ -469,7 +491,7 @@ def kernel_matmul(cov: AbstractKernel, hp, x, V, xp=None, eps: float = EPS_DEFAU
     vec = dV.ndim == 1
     nv = 1 if vec else dV.shape[0]
     O = out if out is not None else (ctx.empty(n) if vec else ctx.empty(nv, n))
-    with _kmm_sym(ctx, symmetric):
+    with _kmm_sym(ctx, symmetric), _kmm_prec(ctx, cov, precision, "fp32"):
         ctx.check(lib.gpr_kernel_matmul(ctx.h, kinds, nk, hpp, d, _ptr(dx), n, _ptr(dxp), m, same,
                                         eps, _ptr(dV), nv, dV.shape[-1], _ptr(O), O.shape[-1]),
                   "gpr_kernel_matmul")
@@ -525,13 +547,15 @@ def kernel_grad_form(cov: AbstractKernel, hp, x, A, B, eps: float = EPS_DEFAULT,
 
 def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: float = 1e-6,
                   maxit: Optional[int] = None, log_scale: bool = False,
-                  eps: float = EPS_DEFAULT, precond_rank: int = 0, symmetric: bool = False):
+                  eps: float = EPS_DEFAULT, precond_rank: int = 0, symmetric: bool = False,
+                  precision: str = "fp64"):
     """The gradient of the negative log marginal likelihood without K, K^{-1} or a factorisation
     (gpr_mll_grad_free): one solve_cg call for [alpha | K^{-1} Z], then kernel_grad_form; the
     trace term is Hutchinson's estimate over the probes Z (N x m; default: ``probes`` standard-
     normal columns from the library's generator at ``seed``, 0 <= seed < 2^31).  ``precond_rank``:
     the rank of the solve's pivoted-Cholesky preconditioner (the knob GPR_CG_PRECOND, set for this
     call and restored).  ``symmetric``: the solve's products by kernel_matmul's symmetric route.
+    ``precision="mixed"``: the solve by solve_cg's refined route (the form itself stays FP64).
     Returns (g, iters, relres)."""
     ctx = md.ctx
     kinds, nk = _kinds_arr(md.covar)
@@ -548,7 +572,7 @@ def mll_grad_free(md: GPRModel, probes: int = 15, seed: int = 0, Z=None, tol: fl
     knob = ctx.get_knob("GPR_CG_PRECOND")
     ctx.set_knob("GPR_CG_PRECOND", int(precond_rank))
     try:
-        with _kmm_sym(ctx, symmetric):
+        with _kmm_sym(ctx, symmetric), _kmm_prec(ctx, md.covar, precision, "mixed"):
             ctx.check(lib.gpr_mll_grad_free(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n,
                                             _ptr(md.dsample()), eps, m, int(seed),
                                             _ptr(dZ), tol, md.n if maxit is None else int(maxit),
@@ -979,7 +1003,7 @@ def predict_mean_from(md: GPRModel, alpha, xp, eps: float = EPS_DEFAULT) -> np.n
 
 def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = None,
              eps: float = EPS_DEFAULT, precond_rank: int = 0, precond_rtol: float = 0.0,
-             symmetric: bool = False):
+             symmetric: bool = False, precision: str = "fp64"):
     """K^{-1} B by conjugate gradients on the matrix a fit factors, every product matrix-free
     (gpr_solve_cg): memory O(N), no preconditioner beyond K's constant diagonal, iterations ~
     sqrt(cond(K)).  B defaults to md.y; maxit to N.  Returns (alpha, iters, relres) with relres
@@ -987,7 +1011,10 @@ def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = Non
     ``precond_rank`` > 0 (at most 256): the pivoted-Cholesky preconditioner of that rank
     (gpr_solve_pcg, ``precond_rtol`` its early stop), which cuts the iterations at small sigma_n; 0
     is the plain call.  ``symmetric``: every product by kernel_matmul's symmetric route (up to 16
-    columns per pass)."""
+    columns per pass).  ``precision="mixed"``: iterative refinement -- the recurrence runs on
+    products with FP32 kernel evaluation (kernel_matmul's "fp32"), every outer step recomputes the
+    residual by one FP64 product, and the call falls back to FP64 products if an outer step gains
+    less than 4 x; iters counts every product and relres is the true FP64 residual as before."""
     ctx = md.ctx
     kinds, nk = _kinds_arr(md.covar)
     hpa, hpp = _hp_arr(md.params)
@@ -997,7 +1024,7 @@ def solve_cg(md: GPRModel, B=None, tol: float = 1e-8, maxit: Optional[int] = Non
     iters = ctypes.c_int(0)
     relres = (ctypes.c_double * nrhs)()
     maxit = md.n if maxit is None else int(maxit)
-    with _kmm_sym(ctx, symmetric):
+    with _kmm_sym(ctx, symmetric), _kmm_prec(ctx, md.covar, precision, "mixed"):
         if precond_rank:
             ctx.check(lib.gpr_solve_pcg(ctx.h, kinds, nk, hpp, md.d, _ptr(md.dx()), md.n, _ptr(dB),
                                         nrhs, dB.shape[-1], eps, tol, maxit, int(precond_rank),

@@ -252,6 +252,27 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         Another summation order, the same elements; workspace stays linear in
  *                         n (at most 64 n nv doubles).  0: every tile, every existing bit.  Wider
  *                         passes and cross kernels ignore it
+ *   GPR_KMM_PREC       0  gpr_kernel_matmul and what is built on it, for sums of SquaredExp, Matern and
+ *                         WhiteNoise parts: 1 evaluates every stationary part's profile in FP32
+ *                         (difference form of the distance on the centred scaled points rounded to
+ *                         FP32, hardware exp2 and sqrt), widens it exactly and feeds the same FP64
+ *                         MFMA product with FP64 accumulators; K's diagonal keeps its FP64 bits and
+ *                         an element is off by about u32 (W dD + 8 k), u32 = 2^-24, beside an
+ *                         absolute 2^-126 sigma^2 (the hardware exp2 flushes smaller results to
+ *                         zero).  Exactly three things follow the knob: every pass of
+ *                         gpr_kernel_matmul, gpr_solve_cg / gpr_solve_pcg, and gpr_mll_grad_free
+ *                         through its solve; gpr_predict's matrix-free mean and
+ *                         gpr_kernel_grad_form keep the FP64 kernels.  The solves
+ *                         then run iterative refinement: the recurrence on the FP32 matrix for
+ *                         K d = r, x += d, r = b - K x by one FP64 product per outer step, and
+ *                         FP64 products for the rest of the call once an outer step gains less than
+ *                         4 x; iters counts every product of either precision, relres stays the true
+ *                         FP64 residual.  With GPR_KMM_SYM = 1 as well the FP32 route takes the full
+ *                         evaluation.  A description with a Periodic part or a product term ignores
+ *                         the knob.  0: every call keeps its code and its bits
+ *   GPR_CG_STAT_OUTER, GPR_CG_STAT_F64   gpr_get_knob only (gpr_set_knob returns GPR_E_ARG, the
+ *                         environment is ignored): the outer steps and the FP64 products of the
+ *                         last refined solve on the context (the products counted in its iters)
  *   GPR_KGF_SLABS      0  gpr_kernel_grad_form: the same for its row blocks (the partial slots are
  *                         added in slab order); 0 auto
  *   GPR_MEAN_FREE     -1  gpr_predict, GPR_PREDICT_MEAN: the mean by the matrix-free product (1)
