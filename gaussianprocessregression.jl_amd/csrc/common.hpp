@@ -343,6 +343,8 @@ struct gpr_ctx {
   int cg_precond = 0;           // GPR_CG_PRECOND: the preconditioner rank gpr_solve_cg uses (0: none)
   DevBuf dgf;                   // matrix-free MLL gradient: [y | Z] and K^{-1} [y | Z] (kgradform.hip)
   int kgf_slabs = 0;            // GPR_KGF_SLABS: the same for gpr_kernel_grad_form's row blocks
+  DevBuf drff;                  // random features: the prepared points and frequencies (rff.hip)
+  int rff_slabs = 0;            // GPR_RFF_SLABS: slabs of gpr_rff_matmul's frequency blocks (0 auto)
   int mean_free = -1;           // GPR_MEAN_FREE: gpr_predict's mean without K(x, xp) (1), with it
                                 // (0), -1 auto: matrix-free when no dwork is passed and n m > 2^29
   // upper-only K assembly for a factorisation (assembly.hip kmat_symu_kernel): its work list

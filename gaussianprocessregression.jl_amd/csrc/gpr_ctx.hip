@@ -314,6 +314,7 @@ const Knob kKnobs[] = {
     {"GPR_CG_STAT_OUTER", &gpr_ctx::cg_outer, nullptr},
     {"GPR_CG_STAT_F64", &gpr_ctx::cg_f64, nullptr},
     {"GPR_KGF_SLABS", &gpr_ctx::kgf_slabs, nullptr},
+    {"GPR_RFF_SLABS", &gpr_ctx::rff_slabs, nullptr},
     {"GPR_MEAN_FREE", &gpr_ctx::mean_free, nullptr},
     {"GPR_CG_PRECOND", &gpr_ctx::cg_precond, nullptr},
 };
@@ -327,7 +328,8 @@ void knob_set(gpr_ctx* ctx, const Knob& k, double v) {
     if (k.ip == &gpr_ctx::dag_rskew || k.ip == &gpr_ctx::dag_rgroup_min) iv = std::max(0, iv);
     if (k.ip == &gpr_ctx::cv_streams) iv = std::max(1, std::min(iv, (int)gpr_ctx::CV_MAX_SUB));
     if (k.ip == &gpr_ctx::pgrad_slab) iv = (std::max(iv, 64) + 63) / 64 * 64;
-    if (k.ip == &gpr_ctx::kmm_slabs || k.ip == &gpr_ctx::kgf_slabs) iv = std::max(0, iv);
+    if (k.ip == &gpr_ctx::kmm_slabs || k.ip == &gpr_ctx::kgf_slabs || k.ip == &gpr_ctx::rff_slabs)
+      iv = std::max(0, iv);
     if (k.ip == &gpr_ctx::cg_precond) iv = std::max(0, std::min(iv, 256));
     if (k.ip == &gpr_ctx::kmm_sym || k.ip == &gpr_ctx::kmm_prec) iv = iv != 0;
     ctx->*k.ip = iv;
@@ -344,7 +346,7 @@ DevBuf gpr_ctx::*const kWorkspaces[] = {
     &gpr_ctx::dgc,    &gpr_ctx::dpadA,    &gpr_ctx::dpadB,      &gpr_ctx::dagb,  &gpr_ctx::deig,
     &gpr_ctx::ddc,    &gpr_ctx::dtri,     &gpr_ctx::dkmm,       &gpr_ctx::dcg,
     &gpr_ctx::dgf,    &gpr_ctx::dpch,     &gpr_ctx::dpchl,      &gpr_ctx::dpchw, &gpr_ctx::dpchcs,
-    &gpr_ctx::dkmf,
+    &gpr_ctx::dkmf,   &gpr_ctx::drff,
 };
 
 const Knob* knob_find(const char* name) {

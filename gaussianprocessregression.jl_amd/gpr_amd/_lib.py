@@ -124,6 +124,8 @@ _SIGS = {
                                     _i, _dp, _dp, _ip]),
     "gpr_split_factors": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p]),
     "gpr_randn": (_i, [_p, c_uint64, c_uint64, _p, c_size_t]),
+    "gpr_rff_draw": (_i, [_p, _ip, _i, _i, _i, c_uint64, _p]),
+    "gpr_rff_matmul": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i]),
     "gpr_mvn_sample": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _p, _i]),
     "gpr_mvn_factor": (_i, [_p, _p, _i, _i, _d, _ip]),
     "gpr_sample_prior": (_i, [_p, _ip, _i, _dp, _i, _p, _i, _p, _d, _d, _p, _i, _i, _p, _i, _p, _i,

@@ -18,7 +18,8 @@ import torch
 from . import _lib
 from ._lib import PosDefException, lib
 from .core import (EPS_DEFAULT, AbstractKernel, Context, GPRModel, GPRPredictCache, _dxp,
-                   _fit_predict, _hp_arr, _kinds_arr, _ptr, default_context, dim_hp)
+                   _fit_predict, _hp_arr, _kinds_arr, _kmm_prec, _ptr, _update_predict_cache,
+                   default_context, dim_hp, is_stationary, part_dim_hp)
 
 SHIFT_DEFAULT = 1e-7  # src/distributions.jl:21
 
@@ -200,3 +201,136 @@ def sample_posterior(md: GPRModel, xp, n_samples: int = 1, z=None, seed: int = 1
     ctx.check(lib.gpr_mvn_sample(ctx.h, _ptr(Sigma), m, m, _ptr(mu), _ptr(dZ), ns, m, _ptr(S), m),
               "gpr_mvn_sample")
     return ctx.host(S).reshape(m, ns)
+
+
+_M64 = 2 ** 64 - 1
+_SEED_W, _SEED_NOISE = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03  # the weights' and the noise's streams
+
+
+class PosteriorPaths:
+    """A joint posterior draw as a function (pathwise conditioning, Matheron's rule):
+
+        f_post(.) = f_prior(.) + K(., x) V,    V = K^{-1} (y 1ᵀ - f_prior(x) - ε),   ε ~ N(0, σ_n² I)
+
+    with f_prior the random-feature function of ``gpr_rff_matmul`` (include/gpr_hip.h) and K the
+    matrix a fit factors.  ``paths(xp)`` returns the m x n_samples values at any xp, at a cost
+    linear in m; the same object evaluated at other points continues the same functions.  On the
+    device it keeps ``omega`` (gpr_rff_draw's layout), ``weights`` (n_samples x 2·nse·n_features:
+    per part the cos block, then the sin block), ``noise`` (the drawn ε, n_samples x N) and ``V``
+    (n_samples x N); ``iters`` and ``relres`` are the CG solve's (None after a factor solve).
+
+    The update term's kernel product centres its Gram form on the first 2048 of its output points;
+    2048 training points (repeated cyclically when N is smaller) are evaluated in front of every
+    batch, so a point's value does not depend on the batch it comes in, as long as the products
+    keep their slab counts (GPR_RFF_SLABS, GPR_KMM_SLABS)."""
+
+    def __init__(self, md: GPRModel, omega, weights, noise, V, n_features: int, eps: float,
+                 iters=None, relres=None):
+        self.md, self.ctx = md, md.ctx
+        self.omega, self.weights, self.noise, self.V = omega, weights, noise, V
+        self.n_features, self.n_samples, self.eps = n_features, V.shape[0], eps
+        self.iters, self.relres = iters, relres
+        with torch.cuda.stream(self.ctx.stream):  # exactly the 2048 rows the centre is taken over
+            self._anchor = md.dx()[torch.arange(2048, device=md.dx().device) % md.n]
+
+    def _prior_(self, dx: torch.Tensor, m: int, dout: torch.Tensor):
+        md, ctx = self.md, self.ctx
+        kinds, nk = _kinds_arr(md.covar)
+        _, hpp = _hp_arr(md.params)
+        ctx.check(lib.gpr_rff_matmul(ctx.h, kinds, nk, hpp, md.d, _ptr(dx), m, _ptr(self.omega),
+                                     self.n_features, _ptr(self.weights), self.n_samples,
+                                     self.weights.shape[-1], _ptr(dout), dout.shape[-1]),
+                  "gpr_rff_matmul")
+
+    def evaluate_(self, dxp: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
+        """dout (n_samples x ldo device tensor, ldo >= m) <- the paths at the device points dxp
+        (m x d tensor: column-major d x m).  Asynchronous on the context's stream."""
+        md, ctx = self.md, self.ctx
+        m, c, ns = dxp.shape[0], self._anchor.shape[0], self.n_samples
+        self._prior_(dxp, m, dout)
+        kinds, nk = _kinds_arr(md.covar)
+        _, hpp = _hp_arr(md.params)
+        with torch.cuda.stream(ctx.stream):
+            xa = torch.cat([self._anchor, dxp.reshape(m, md.d)])
+        upd = ctx.empty(ns, c + m)
+        ctx.check(lib.gpr_kernel_matmul(ctx.h, kinds, nk, hpp, md.d, _ptr(xa), c + m, _ptr(md.dx()),
+                                        md.n, _lib.GPR_CROSS, self.eps, _ptr(self.V), ns, md.n,
+                                        _ptr(upd), c + m), "gpr_kernel_matmul")
+        with torch.cuda.stream(ctx.stream):
+            dout[:, :m] += upd[:, c:]
+        return dout
+
+    def __call__(self, xp) -> np.ndarray:
+        ctx = self.ctx
+        dxp = ctx.colmajor(xp).reshape(-1, self.md.d)
+        return ctx.host(self.evaluate_(dxp, ctx.empty(self.n_samples, dxp.shape[0])))
+
+    def __repr__(self):
+        return (f"PosteriorPaths(n_samples={self.n_samples}, n_features={self.n_features}, "
+                f"N={self.md.n})")
+
+
+def sample_paths(md: GPRModel, n_samples: int = 1, n_features: int = 1024, seed: int = 1,
+                 solver: str = "factor", tol: float = 1e-8, maxit: int = 1000,
+                 eps: float = EPS_DEFAULT, precision: Optional[str] = None,
+                 precond_rank: Optional[int] = None) -> PosteriorPaths:
+    """``n_samples`` joint posterior draws as one function object (PosteriorPaths): unlike
+    sample_posterior nothing m x m is formed, the draw can be evaluated at any later xp, and two
+    evaluations belong to the same functions.  Sums of SquaredExp, Matern and WhiteNoise parts (a
+    Periodic part or a product raises GprError from the library); 1-D y.  ``n_features``
+    frequencies per stationary part (2 n_features features); the prior's covariance is off by
+    O(1 / sqrt(n_features)).  Ω, the weights and ε come from gpr_randn's streams of ``seed``.
+
+    ``solver="factor"``: fits as sample_posterior does and solves the n_samples columns by
+    gpr_potrs_upper -- O(N²) memory, and its sweeps are slow for hundreds of columns (fine up to
+    about 64).  ``solver="cg"``: gpr_solve_cg to ``tol`` in at most ``maxit`` iterations, K never
+    formed; ``precision`` ("fp64" / "mixed") and ``precond_rank`` as solve_cg's."""
+    if md.y.ndim != 1:
+        raise ValueError("sample_paths needs a 1-D y")
+    if solver not in ("factor", "cg"):
+        raise ValueError(f'solver must be "factor" or "cg", not {solver!r}')
+    ns, F = int(n_samples), int(n_features)
+    if ns < 1 or F < 1:
+        raise ValueError("n_samples and n_features must be >= 1")
+    ctx, d, n = md.ctx, md.d, md.n
+    kinds, nk = _kinds_arr(md.covar)
+    _, hpp = _hp_arr(md.params)
+    nse = sum(1 for k in md.covar.kinds() if k not in (_lib.GPR_WN, _lib.GPR_MUL))
+    seed = int(seed) & _M64
+    omega = ctx.empty(max(nse, 1) * d * F)
+    ctx.check(lib.gpr_rff_draw(ctx.h, kinds, nk, d, F, seed, _ptr(omega)), "gpr_rff_draw")
+    rows = 2 * nse * F
+    W, noise, R = ctx.empty(ns, rows), ctx.empty(ns, n), ctx.empty(ns, n)
+    ctx.check(lib.gpr_randn(ctx.h, seed ^ _SEED_W, 0, _ptr(W), rows * ns), "gpr_randn")
+    ctx.check(lib.gpr_randn(ctx.h, seed ^ _SEED_NOISE, 0, _ptr(noise), n * ns), "gpr_randn")
+    sigma_n, off = 0.0, 0  # the first WhiteNoise's, as everywhere else
+    for part in md.covar.parts():
+        if not is_stationary(part):
+            sigma_n = float(md.params[off])
+            break
+        off += part_dim_hp(part, d)
+    paths = PosteriorPaths(md, omega, W, noise, R, F, eps)
+    paths._prior_(md.dx(), n, R)
+    with torch.cuda.stream(ctx.stream):
+        noise.mul_(sigma_n)
+        R.neg_().sub_(noise).add_(md.dsample()[None, :])  # y 1ᵀ - f_prior(x) - ε
+    if solver == "factor":
+        pc = GPRPredictCache(md, 0)
+        _update_predict_cache(pc, md, eps)
+        ctx.check(lib.gpr_potrs_upper(ctx.h, _ptr(pc.Kxx), n, pc.ld, _ptr(R), ns, n),
+                  "gpr_potrs_upper")
+        ctx.sync()  # (the factor is freed with pc)
+        return paths
+    X = ctx.empty(ns, n)
+    iters, relres = ctypes.c_int(0), (ctypes.c_double * ns)()
+    with _kmm_prec(ctx, md.covar, precision or "fp64", "mixed"):
+        if precond_rank:
+            ctx.check(lib.gpr_solve_pcg(ctx.h, kinds, nk, hpp, d, _ptr(md.dx()), n, _ptr(R), ns, n,
+                                        eps, tol, int(maxit), int(precond_rank), 0.0, _ptr(X), n,
+                                        ctypes.byref(iters), relres, None), "gpr_solve_pcg")
+        else:
+            ctx.check(lib.gpr_solve_cg(ctx.h, kinds, nk, hpp, d, _ptr(md.dx()), n, _ptr(R), ns, n,
+                                       eps, tol, int(maxit), _ptr(X), n, ctypes.byref(iters),
+                                       relres), "gpr_solve_cg")
+    paths.V, paths.iters, paths.relres = X, iters.value, np.array(relres[:])
+    return paths

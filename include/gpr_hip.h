@@ -275,6 +275,9 @@ int gpr_set_outer_block(gpr_ctx_t ctx, int nb2);
  *                         last refined solve on the context (the products counted in its iters)
  *   GPR_KGF_SLABS      0  gpr_kernel_grad_form: the same for its row blocks (the partial slots are
  *                         added in slab order); 0 auto
+ *   GPR_RFF_SLABS      0  gpr_rff_matmul: slabs the (part, 64-frequency block) list is cut into per
+ *                         64 points (partials added in slab order); 0 auto: the fewest that give
+ *                         two workgroups per CU, at most 64
  *   GPR_MEAN_FREE     -1  gpr_predict, GPR_PREDICT_MEAN: the mean by the matrix-free product (1)
  *                         or through K(x, xp) (0); -1 auto: matrix-free only when dwork is NULL
  *                         and the scratch it replaces would pass 4 GiB (n m > 2^29)
@@ -602,6 +605,45 @@ int gpr_fit_predict(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, i
  * likewise from (w3, w2), r = sqrt(-2 ln u1); element g = r cos(2 pi u2) for even g,
  * r sin(2 pi u2) for odd g.  Asynchronous. */
 int gpr_randn(gpr_ctx_t ctx, uint64_t seed, uint64_t offset, double* dZ, size_t count);
+
+/* ---- random-feature prior functions (pathwise posterior sampling; no reference counterpart) --
+ * For a sum of GPR_SE / GPR_M32 / GPR_M52 (and GPR_WN) parts, F = nfreq frequencies per stationary
+ * part p and raw (uncentred) x:
+ *   t_pj(x)       = sum_k Omega_p[j, k] l_pk x_k                                          (j < F)
+ *   f_prior(x)[c] = sum_p (sigma_p / sqrt(F)) sum_j (A_p[j, c] cos(2 pi t_pj(x)) + B_p[j, c] sin(2 pi t_pj(x)))
+ * With A_p, B_p standard normal and Omega_p from gpr_rff_draw, f_prior is a draw from the prior GP
+ * up to O(1 / sqrt(F)): (1/F) sum_j cos(2 pi (t_pj(x) - t_pj(x'))) -> k_p(x, x') / sigma_p^2.
+ *
+ * gpr_rff_draw writes Omega for the nse stationary parts in part order: nse blocks of nfreq x d,
+ * column-major inside a block (Omega_p[j, k] at p nfreq d + j + k nfreq).  Omega depends on the
+ * part's kind only, never on hp; with z ~ N(0, I_d)
+ *   GPR_SE   Omega = sqrt(2) z / (2 pi)                    (k = sigma^2 exp(-D), no 1/2)
+ *   GPR_M32  Omega = z sqrt(3 / g) / (2 pi),  g = the sum of 3 squared standard normals
+ *   GPR_M52  Omega = z sqrt(5 / g) / (2 pi),  g = the sum of 5 squared standard normals.
+ * The normals are elements of gpr_randn's stream of `seed`: z_k of (part p, frequency j) is element
+ *   p 2^56 + j 2^24 + k,   and the i-th normal of g is element   p 2^56 + j 2^24 + 2^24 - 8 + i,
+ * so an element of Omega depends on (seed, p, j, k) alone: a call with a smaller nfreq returns the
+ * first frequencies of a larger one.  d <= 2^24 - 8, at most 256 stationary parts.  A GPR_PER part
+ * (a line spectrum) or a GPR_MUL marker (a convolution of spectra): GPR_E_UNSUP, naming the part;
+ * no stationary part, a NULL pointer, d or nfreq < 1: GPR_E_ARG.  Asynchronous. */
+int gpr_rff_draw(gpr_ctx_t ctx, const int* kinds, int nk, int d, int nfreq, uint64_t seed,
+                 double* dOmega);
+
+/* Out[n x ns] (ldo) = f_prior(X) as defined above, X d x n as everywhere; dOmega as gpr_rff_draw
+ * lays it out; W (ldw) has 2 nse nfreq rows -- per stationary part the cos block A_p (nfreq rows),
+ * then the sin block B_p -- and ns columns.  The n x 2 nse nfreq feature matrix is never stored:
+ * 64 x 64 tiles of t come from an FP64 MFMA over k = d, r = t - rint(t) is exact (that is why
+ * Omega carries the 1 / (2 pi)), sin(2 pi r) and cos(2 pi r) come from one octant reduction and two
+ * polynomials (within 3 u of the exact values), and a second FP64 MFMA multiplies by the weights,
+ * into which sigma_p / sqrt(F) is folded.  Workspace is linear in n + nfreq; nothing of size
+ * n nfreq is allocated.  No atomics: two calls agree bit for bit (GPR_RFF_SLABS changes the
+ * summation order, nothing else).  Asynchronous on the context's stream.  Refused before
+ * anything is written -- GPR_E_UNSUP, naming the part: a GPR_PER part or a GPR_MUL marker;
+ * GPR_E_ARG, naming the argument: a NULL pointer, n, nfreq or ns < 1, ldw < 2 nse nfreq, ldo < n,
+ * a description with no stationary part. */
+int gpr_rff_matmul(gpr_ctx_t ctx, const int* kinds, int nk, const double* hp, int d,
+                   const double* dX, int n, const double* dOmega, int nfreq, const double* dW,
+                   int ns, int ldw, double* dOut, int ldo);
 
 /* S (n x ns, lds) = mu 1^T + U^T Z: s .= N.Sigma_ch.L * s .+ N.mu (src/distributions.jl:28) for
  * ns draws at once.  U = the upper triangle of the factor buffer dU (n x n, ldu; from
